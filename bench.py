@@ -80,6 +80,20 @@ host cores, median of 3 dispatches, plus a 1-thread sample and the other
 configs' row subsets (oracle/cpu_baseline.py, child process, N=1 only).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config2|config3|config4|config5|shipped]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs: it sets up, warms up, times
+the K steps and prints the line (value, ms_per_step, config, roofline, timing).
+--full adds everything else described above, each in runs of its own after
+the timed steps: `verified`, `single_frame`, `draw_loop`, `pipelined`,
+`rgba8_surface`, `general_kernel`, `independent_frames` and `cpu_baseline`
+(the --no-* options drop single ones again).
+--dump-outputs DIR writes what the last timed step rendered (rank 0: the
+frames it assembled at N>1, else its output buffer) as DIR/<name>.npy, float32
+(pixels, channels), with the pixels' indices in DIR/<name>_pixel_index.npy:
+all of them, or a fixed seeded sample of 2^21 draws when there are more. The
+scene, the views and the sample are functions of the arguments alone, so two
+builds can be compared output for output.
 
 --gpus N > 1 runs under torch.distributed.run (one rank per GPU, as the driver
 launches it) or on its own: with WORLD_SIZE unset, this process starts the N
@@ -171,7 +185,49 @@ def parse():
                     help="config2, shipped at N=1: skip the general-kernel (scene shapes off) measurement")
     ap.add_argument("--no-single-frame", action="store_true",
                     help="config2, config3 at N=1: skip the one-frame-per-launch measurement (profiling runs: one launch shape)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the verification of the last timed step, "
+                         "the secondary measurements (single_frame, draw_loop, pipelined, rgba8_surface, "
+                         "general_kernel, independent_frames) and the llvmpipe CPU baseline; each --no-* option "
+                         "above drops one of them again. Without --full a run sets up, warms up, times the steps "
+                         "and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step rendered to DIR/<name>.npy "
+                         "(float32 values, float64 pixel indices; a fixed seeded sample of the pixels when the "
+                         "output is larger than the dump's budget)")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run does only what the headline figure needs
+        args.no_verify = args.no_independent = args.no_cpu_baseline = True
+        args.no_single_frame = args.no_pipelined = args.no_rgba8 = args.no_general = True
+    return args
+
+
+DUMP_PIXELS = 1 << 21  # at most this many pixels per dump: 32 MB of float4 values + 16 MB of float64 indices
+DUMP_SEED = 20240
+
+
+def dump_outputs(torch, out_dir, name, buf, channels):
+    """Write the output buffer of the last timed step as out_dir/<name>.npy:
+    float32 (pixels, channels), GL_RGBA8 texels and RGB8 bytes as their byte
+    values. A buffer of more than DUMP_PIXELS pixels is sampled: the sorted
+    distinct indices of DUMP_PIXELS seeded draws over its pixels, the same on
+    every run of the same arguments, written beside it as
+    <name>_pixel_index.npy (float64; exact below 2^53)."""
+    if buf.dtype == torch.int32:  # GL_RGBA8 surface: one texel per element
+        px = buf.reshape(-1).view(torch.uint8).reshape(-1, 4)
+    else:
+        px = buf.reshape(-1, channels)
+    n = px.shape[0]
+    if n > DUMP_PIXELS:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_PIXELS))
+    else:
+        idx = np.arange(n, dtype=np.int64)
+    got = px.index_select(0, torch.as_tensor(idx, device=px.device)) if n > DUMP_PIXELS else px
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), got.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(out_dir, name + "_pixel_index.npy"), idx.astype(np.float64))
+    return {"name": name, "pixels": int(idx.size), "of": int(n), "channels": int(got.shape[1])}
 
 
 def frame_time(k):
@@ -743,6 +799,7 @@ def main():
                 at.start(it, comm_s)
             if rank == 0:
                 total.mul_(1.0 / spp)  # the estimate: mean over all samples
+            plan.last = total
             if timed:
                 at.stop(it, comm_s)
 
@@ -881,6 +938,20 @@ def main():
         plan = frame_plan()
 
     elapsed, avg_kernel_ms, per_rank = measure(plan, args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left for its caller: the frames rank 0
+        # assembled (N>1), else the buffer its last step rendered into
+        torch.cuda.synchronize()
+        if mc:
+            out_name, out_buf, out_ch = "estimate", plan.last, 4
+        elif plan.last is not None:
+            out_name, out_buf = "assembled_frames", plan.last
+            out_ch = 3 if (out_buf.dtype == torch.uint8 or not batched) else surfaces[surf][1]
+        else:
+            out_name, out_buf = "frames", plan.bufs[(args.steps - 1) % len(plan.bufs) if plan.per_launch else 0]
+            out_ch = surfaces[surf][1] if batched else 4 if world == 1 else 3
+        dumped = dump_outputs(torch, args.dump_outputs, out_name, out_buf, out_ch)
     verified = None
     if batched and world == 1 and not args.no_verify:
         # N=1: frames of the last timed step (the first, middle and last of
@@ -1180,6 +1251,8 @@ def main():
                                                                                       pmc["stale_build"])
         if verified is not None:
             line["verified"] = verified
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if world > 1:
             # DESIGN.md §6's prediction of this step from the committed
             # one-GPU shard timings, beside the measured ms_per_step

@@ -21,7 +21,7 @@ def run_bench(n, *args, timeout=240):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"),
-           "--gpus", str(n), "--dist-backend", "gloo", "--no-cpu-baseline", *args]
+           "--gpus", str(n), "--dist-backend", "gloo", "--full", "--no-cpu-baseline", *args]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -155,7 +155,7 @@ def test_config3_one_gpu_batches_frames():
     carries the one-frame-per-launch rate of the same frames, on one stream
     and on two, and the two-stream step rate."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "config3", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -225,7 +225,8 @@ def test_config2_one_gpu_line_checks_itself():
     figure is the kernel's own (kernel time x launches per step within
     [0.97, 1.01] of the step time, for the float4 line and for the GL_RGBA8
     surface); the single-frame rates are medians of 3 repeats."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--full",
+           "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -302,7 +303,7 @@ def test_self_launched_two_ranks_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-                        "--no-cpu-baseline", "--steps", "3", "--warmup", "1", "--frames", "4"],
+                        "--full", "--no-cpu-baseline", "--steps", "3", "--warmup", "1", "--frames", "4"],
                        capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -312,7 +313,7 @@ def test_self_launched_two_ranks_on_one_gpu():
 
 
 def _bench_line(*args, timeout=300):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", *args]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", *args]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -345,3 +346,98 @@ def test_one_frame_workloads_verify_what_they_time(workload):
     line = _bench_line("--workload", workload, "--steps", "1", "--warmup", "1", "--no-pipelined")
     v = line["verified"]
     assert v["bit_exact"] and v["mismatched_pixels"] == 0 and len(v["rows"]) == 2
+
+
+SECONDARY = ("verified", "single_frame", "pipelined", "rgba8_surface", "general_kernel", "draw_loop",
+             "independent_frames")
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_plain_run_skips_what_full_adds(monkeypatch):
+    """Without --full every secondary measurement, the verification and the
+    CPU baseline are off; --full leaves them to their --no-* options."""
+    bench = _load_bench()
+    offs = ("no_verify", "no_independent", "no_cpu_baseline", "no_single_frame", "no_pipelined", "no_rgba8",
+            "no_general")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    plain = bench.parse()
+    assert not plain.full and plain.steps == 7 and plain.warmup == 2 and plain.dump_outputs is None
+    assert all(getattr(plain, k) for k in offs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-rgba8", "--dump-outputs", "d"])
+    full = bench.parse()
+    assert full.full and full.dump_outputs == "d"
+    assert [k for k in offs if getattr(full, k)] == ["no_rgba8"]
+
+
+def test_dump_outputs_writes_whole_small_buffers_and_seeded_samples(tmp_path, monkeypatch):
+    """bench.dump_outputs on host tensors: a small float4 buffer is written
+    whole; a buffer above the budget as the same seeded sample every time,
+    with its pixel indices; GL_RGBA8 texels as their four byte values."""
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    buf = torch.arange(5 * 7 * 4, dtype=torch.float32)
+    rec = bench.dump_outputs(torch, str(tmp_path / "a"), "frames", buf, 4)
+    got = np.load(tmp_path / "a" / "frames.npy")
+    assert rec == {"name": "frames", "pixels": 35, "of": 35, "channels": 4}
+    assert got.dtype == np.float32 and np.array_equal(got, buf.numpy().reshape(35, 4))
+    assert np.array_equal(np.load(tmp_path / "a" / "frames_pixel_index.npy"), np.arange(35, dtype=np.float64))
+    monkeypatch.setattr(bench, "DUMP_PIXELS", 16)
+    texels = torch.arange(1000, dtype=torch.int32) * 65793  # bytes (k, k, k, 0) for k < 256
+    for d in ("b", "c"):
+        rec = bench.dump_outputs(torch, str(tmp_path / d), "frames", texels, 1)
+    idx = np.load(tmp_path / "b" / "frames_pixel_index.npy")
+    val = np.load(tmp_path / "b" / "frames.npy")
+    assert idx.dtype == np.float64 and 1 < idx.size <= 16 and np.all(np.diff(idx) > 0) and idx.max() < 1000
+    assert rec["pixels"] == idx.size and rec["of"] == 1000 and val.shape == (idx.size, 4)
+    want = texels.numpy()[idx.astype(np.int64)].view(np.uint8).reshape(-1, 4).astype(np.float32)
+    assert np.array_equal(val, want)
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "frames_pixel_index.npy"))
+    assert np.array_equal(val, np.load(tmp_path / "c" / "frames.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path, gpu_ctx):
+    """`bench.py --gpus 1 --steps K --warmup W` alone: the headline fields
+    and none of --full's; --dump-outputs writes a seeded sample of the last
+    timed step's frames, equal bit for bit to a render of the same views
+    made here (2 frames of config 2: more pixels than the dump keeps)."""
+    import numpy as np
+    import torch
+
+    import openglraytracer_amd as rt
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--frames", "2", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["value"] == pytest.approx(2 * 1920 * 1080 / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+    assert line["cpu_baseline"] is None and not [k for k in SECONDARY if k in line]
+    W, H, F = 1920, 1080, 2
+    val = np.load(out / "frames.npy")
+    idx = np.load(out / "frames_pixel_index.npy").astype(np.int64)
+    assert sorted(p.name for p in out.iterdir()) == ["frames.npy", "frames_pixel_index.npy"]
+    assert val.dtype == np.float32 and val.shape == (idx.size, 4) and val.nbytes + 8 * idx.size <= 64 << 20
+    assert 1 << 20 < idx.size <= 1 << 21 and np.all(np.diff(idx) > 0) and idx[-1] < F * H * W
+    assert line["dumped_outputs"] == {"name": "frames", "pixels": idx.size, "of": F * H * W, "channels": 4}
+    scene = rt.Scene(gpu_ctx, rt.bench_objects(16, 0))
+    ref = torch.zeros((F * H * W, 4), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    gpu_ctx.set_output(rt.abi.RT_OUTPUT_RGBA32F)
+    rt.render_batch(gpu_ctx, scene, ref.data_ptr(), W, H, 0, [rt.make_view(None, k / 60.0) for k in range(F)])
+    torch.cuda.synchronize()
+    want = ref[torch.as_tensor(idx, device="cuda")].cpu().numpy()
+    scene.close()
+    assert np.array_equal(val.view(np.uint32), want.view(np.uint32))

@@ -36,17 +36,17 @@ if [ "$what" = prof ] || [ "$what" = all ]; then
   mkdir -p $out/profiles && cp profiles/${tag}_* profiles/pmc_*latest.json $out/profiles/
 fi
 if [ "$what" = bench ] || [ "$what" = all ]; then
-  run bench_config2 300 python bench.py
-  run bench_config3 300 python bench.py --workload config3 --steps 20 --warmup 3 --no-cpu-baseline
-  run bench_config4 300 python bench.py --workload config4 --steps 5 --warmup 1 --no-cpu-baseline
-  run bench_config5 300 python bench.py --workload config5 --steps 3 --warmup 1 --no-cpu-baseline
-  run bench_shipped 300 python bench.py --workload shipped
+  run bench_config2 300 python bench.py --full
+  run bench_config3 300 python bench.py --full --workload config3 --steps 20 --warmup 3 --no-cpu-baseline
+  run bench_config4 300 python bench.py --full --workload config4 --steps 5 --warmup 1 --no-cpu-baseline
+  run bench_config5 300 python bench.py --full --workload config5 --steps 3 --warmup 1 --no-cpu-baseline
+  run bench_shipped 300 python bench.py --full --workload shipped
   run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
   # several ranks share the one GPU here (gloo): the step structure and the
   # byte-exact assembly, not scaling figures
-  run selflaunch_config2_n2 400 python bench.py --gpus 2 --dist-backend gloo --steps 5 --warmup 2 --frames 64 \
+  run selflaunch_config2_n2 400 python bench.py --full --gpus 2 --dist-backend gloo --steps 5 --warmup 2 --frames 64 \
       --no-cpu-baseline
   run gloo_config2_n4 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-      --master-port 29611 bench.py --gpus 4 --dist-backend gloo --steps 5 --warmup 2 --frames 64 --no-cpu-baseline
+      --master-port 29611 bench.py --full --gpus 4 --dist-backend gloo --steps 5 --warmup 2 --frames 64 --no-cpu-baseline
 fi
 echo done
