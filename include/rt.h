@@ -348,6 +348,15 @@ int rt_multi_last_ms(rt_multi *m, float *kernel_ms, float *gather_ms, float *ass
  * translate-only box holding every live light). 0: every render runs the
  * general kernel. Output is identical. */
 #define RT_OPT_SCENE_SHAPES 8
+/* RT_OPT_LAUNCH_SHAPES (default 1): a depth-0 render that runs a scene-shape
+ * kernel and is a whole-frame float4 render — unsharded, all rows, the
+ * RT_OUTPUT_RGBA32F surface, the host's frame constants (RT_OPT_FRAME_CONSTS),
+ * at least 2 x 2 pixels, every view's camera within the short perspective
+ * divisions' range, no accumulation — runs that kernel compiled for this
+ * launch shape as well: none of the launch's own uniform tests (shard
+ * mapping, surface format, division form) is made at run time. 0: every
+ * render reads them at run time. Output is identical. */
+#define RT_OPT_LAUNCH_SHAPES 9
 /* (option 6, a tolerance tier that summed the recursion's colours forward
  * instead of mixing them on the way back up, measured even with the exact
  * walk and was removed: DESIGN.md §3.) */

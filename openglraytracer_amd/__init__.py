@@ -237,6 +237,12 @@ class Context:
         live light). Output identical either way."""
         _check(lib().rt_context_set(self._h, abi.RT_OPT_SCENE_SHAPES, 1 if on else 0))
 
+    def set_launch_shapes(self, on):
+        """RT_OPT_LAUNCH_SHAPES: a whole-frame float4 depth-0 render of a
+        shaped scene runs the kernel compiled for that launch shape too
+        (include/rt.h). Output identical either way."""
+        _check(lib().rt_context_set(self._h, abi.RT_OPT_LAUNCH_SHAPES, 1 if on else 0))
+
     def set_output(self, fmt):
         """RT_OPT_OUTPUT: abi.RT_OUTPUT_RGBA32F (float4 per pixel),
         abi.RT_OUTPUT_RGBA8 (the shipped GL_RGBA8 surface, 4 bytes per pixel)

@@ -261,6 +261,9 @@ struct LaunchParams {
     // camera terms (the primary rays compute them as secondary rays do: the
     // same arithmetic, so the same values) — 16 B less per sphere per view
     int32_t lean_views;
+    // host only: RT_OPT_LAUNCH_SHAPES, the depth-0 shaped kernels may take the
+    // launch's shape (launch_shape)
+    int32_t shape_launch;
 };
 // ROCm passes kernel arguments above 4 KiB (an 8 KB argument block checked on
 // MI355X); this block stays under 6 KiB.
@@ -279,6 +282,17 @@ constexpr int kShapeMaskTexels = 12;  // the LDS masks' texels per face edge in 
 constexpr int kShapeRoom = 16;
 constexpr int kShapeWide = 32;
 int scene_shape(const LaunchParams &p, int max_depth);
+// Launch shapes (render_kernel<D, ..., kShape, kLaunch>, the depth-0 shaped
+// kernels without accumulation): the launch's own uniform answers as
+// compile-time constants, a bit per shape; 0: everything read at run time.
+// kLaunchPlain, the whole-frame float4 render (rt_render's draw, an unsharded
+// rt_render_batch): whole unsharded rows (n_shards <= 0, row_begin = 0,
+// n_rows = height, one slice), the RGBA32F surface, cam_short = 1, the host's
+// frame constants present, width and height >= 2. Chosen per launch on the
+// host (launch_shape) from the parameters alone; RT_OPT_LAUNCH_SHAPES 0
+// (LaunchParams::shape_launch) forces 0.
+constexpr int kLaunchPlain = 1;
+int launch_shape(const LaunchParams &p, int max_depth);
 // Lean views (LaunchParams::lean_views): the wide-shape kernels.
 constexpr bool kLeanViews(int shape) { return (shape & kShapeWide) != 0; }
 // 16-B records of one view's per-frame constants in LDS: the spheres' camera
@@ -396,6 +410,7 @@ struct rt_context {
     int host_consts = 1;  // RT_OPT_FRAME_CONSTS
     int origin_lists = 1;  // RT_OPT_ORIGIN_LISTS
     int scene_shapes = 1;  // RT_OPT_SCENE_SHAPES
+    int launch_shapes = 1;  // RT_OPT_LAUNCH_SHAPES
     // device-side view batches (> kMaxViews views): per slot a device buffer,
     // its pinned host staging and an event after the last launch that read it
     void *batch_dev[rtamd::kBatchSlots] = {};

@@ -136,8 +136,8 @@ __device__ __forceinline__ float inv_sqrt(float d) {
 #endif
     // d in [2^-96, 2^100] as one unsigned compare of the bit pattern (NaN and
     // negative d fall outside), so the vote takes the compare's lane mask
-    if (wave_all(__float_as_uint(d) - __float_as_uint(0x1p-96f) <=
-                 __float_as_uint(0x1p100f) - __float_as_uint(0x1p-96f)))
+    if (__builtin_expect(wave_all(__float_as_uint(d) - __float_as_uint(0x1p-96f) <=
+                                  __float_as_uint(0x1p100f) - __float_as_uint(0x1p-96f)), 1))
         return rcp_refined(sqrt_short(d)).r;
     return 1.0f / sqrtf(d);
 }
@@ -167,7 +167,7 @@ __device__ __forceinline__ v3 normalize_unit(v3 a) {
 #ifdef RT_FAST_RSQ
     return muls(a, __builtin_amdgcn_rsqf(d));
 #endif
-    if (wave_all(near_one(d))) return muls(a, inv_sqrt_near_one(d));
+    if (__builtin_expect(wave_all(near_one(d)), 1)) return muls(a, inv_sqrt_near_one(d));
     return muls(a, inv_sqrt(d));
 }
 __device__ __forceinline__ float gmin(float a, float b) { return a < b ? a : b; }
@@ -516,9 +516,9 @@ __device__ __forceinline__ bool slab_may_hit(const BoxRec &b, v3 rs, v3 rd, floa
 // within 2^-16 of |d| (correctly rounded division is monotonic).
 __device__ __forceinline__ bool quotient_below_one(float num, float d) {
     const float an = fabsf(num), ad = fabsf(d);
-    if (an > 1e-30f && ad > 1e-30f) {
+    if (__builtin_expect(an > 1e-30f && ad > 1e-30f, 1)) {
         if (an > ad * 1.0000153f) return false;
-        if (an < ad * 0.9999847f) return true;
+        if (__builtin_expect(an < ad * 0.9999847f, 1)) return true;
     }
     return fdiv(num, d) < 1.0f;
 }
@@ -584,7 +584,7 @@ __device__ __forceinline__ float sphere_sqrt(float qd) {
 #ifdef RT_FAST_SQRT
     return __builtin_amdgcn_sqrtf(qd);
 #endif
-    if (wave_all(qd >= 0x1p-96f)) return sqrt_short(qd);
+    if (__builtin_expect(wave_all(qd >= 0x1p-96f), 1)) return sqrt_short(qd);
     return sqrtf(qd);
 }
 // intersect_sphere_object's t (:586-625) from the ray-invariant terms.
@@ -593,7 +593,7 @@ __device__ __forceinline__ float sphere_t(float qb, float qc, float qa2, float q
     if (qd < 0.0f) return -1.0f;
     const float sq = sphere_sqrt(qd);
     const float n1 = -qb + sq, n2 = -qb - sq;
-    if (fminf(fabsf(n1), fabsf(n2)) >= floor) {
+    if (__builtin_expect(fminf(fabsf(n1), fabsf(n2)) >= floor, 1)) {
         // (the quotient in every lane and a select for t_far < 0 measured
         // slower: config 4 16.57 -> 16.79 ms)
         if (n1 < 0.0f) return -1.0f;  // t_far < 0
@@ -617,7 +617,7 @@ __device__ __forceinline__ bool sphere_blocks(float qb, float qc, float qa2, flo
     if (!(qd >= 0.0f)) return false;
     const float sq = sphere_sqrt(qd);
     const float n1 = -qb + sq, n2 = -qb - sq;
-    if (fminf(fabsf(n1), fabsf(n2)) >= floor) {
+    if (__builtin_expect(fminf(fabsf(n1), fabsf(n2)) >= floor, 1)) {
         if (n1 < 0.0f) return false;
         const float n = n2 < 0.0f ? n1 : n2;
         return n > 0.0f && quotient_below_one(n, qa2);
@@ -863,7 +863,7 @@ __device__ __forceinline__ int direction_texel(int n, v3 u) {
     const float ma = fabsf(__builtin_amdgcn_cubema(u.x, u.y, u.z));  // 2 |major|
     // (computed in every lane and selected instead of the early return:
     // measured even, r02k)
-    if (!(ma > 2e-20f && ma < 2e30f)) return -1;
+    if (__builtin_expect(!(ma > 2e-20f && ma < 2e30f), 0)) return -1;
     const float h = static_cast<float>(n) * __builtin_amdgcn_rcpf(ma);
     const int col = min(max(static_cast<int>(floorf(sc * h + 0.5f * n)), 0), n - 1);
     const int row = min(max(static_cast<int>(floorf(tc * h + 0.5f * n)), 0), n - 1);
@@ -872,7 +872,7 @@ __device__ __forceinline__ int direction_texel(int n, v3 u) {
 // (nbits: the mask's sphere and box bits)
 __device__ __forceinline__ uint64_t direction_mask(const void *tab, int n, int bytes, v3 u, int nbits) {
     const int at = direction_texel(n, u);
-    if (at < 0) return nbits >= 64 ? ~uint64_t{0} : (uint64_t{1} << nbits) - 1u;
+    if (__builtin_expect(at < 0, 0)) return nbits >= 64 ? ~uint64_t{0} : (uint64_t{1} << nbits) - 1u;
     if (bytes == 8) return static_cast<const uint64_t *>(tab)[at];
     return bytes == 2 ? static_cast<const uint16_t *>(tab)[at] : static_cast<const uint32_t *>(tab)[at];
 }
@@ -1572,7 +1572,11 @@ __device__ __forceinline__ void trace_tree(const Scene &S, Ray ray, bool active,
 // power-of-two block (the bench's 8) takes shifts: the integer division it
 // replaces expands to a long VALU / SALU sequence, once per lane and eight
 // times per wave tile.
+// (kLaunch: the launch's shape as constants, rt_internal.h kLaunchPlain —
+// whole unsharded frames, so a local row is its frame row)
+template <int kLaunch = 0>
 __device__ __forceinline__ int output_row(const LaunchParams &p, int local) {
+    if constexpr ((kLaunch & kLaunchPlain) != 0) return local;
     if (p.n_shards <= 0) return p.row_begin + local;
     const int b = p.block_rows;
     if ((b & (b - 1)) == 0) {
@@ -1592,8 +1596,14 @@ __device__ __forceinline__ uint32_t unorm8(float v) {
 
 // One pixel's colour into the launch's surface (float4 or GL_RGBA8 bytes);
 // idx = local_row * width + x (< 2^32: 65536 x 65536 frames at most).
+template <int kLaunch = 0>
 __device__ __forceinline__ void store_pixel(const LaunchParams &p, int z, uint32_t idx, v3 col) {
-    const size_t at = static_cast<size_t>(z) * p.n_rows * p.width + idx;
+    constexpr bool kPlain = (kLaunch & kLaunchPlain) != 0;  // the float4 surface, whole frames
+    const size_t at = static_cast<size_t>(z) * (kPlain ? p.height : p.n_rows) * p.width + idx;
+    if constexpr (kPlain) {
+        p.out[at] = make_float4(col.x, col.y, col.z, 0.0f);
+        return;
+    }
     if (p.out_format == RT_OUTPUT_RGBA8) {  // GL_RGBA8 unorm store of vec4(rgb, 0.0) (main.cpp:223, :404): rt_pack_rgba8
         reinterpret_cast<uint32_t *>(p.out)[at] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16);
     } else if (p.out_format == RT_OUTPUT_RGB32F) {  // packed float3, the constant alpha dropped
@@ -1653,9 +1663,14 @@ __device__ __forceinline__ float jitter_u(uint32_t seed, uint32_t sample, uint32
 // (profiles/r06y_ab_lean_views.log); 5 waves +9 %
 #define RT_WPE_WIDE 7
 #endif
+// the general depth-0 kernel (kShape 0: every scene feature read at run
+// time) at 7 waves, 72 VGPRs: config 2 with the scene shapes off -5 %, frames
+// identical (round 6 item 16); the shaped kernels fit 64 and keep 8
+// (a fixed value, not a build switch: RT_WPE0 still overrides the shaped ones)
+#define RT_WPE0_GENERAL 7
 #define RT_WAVES_PER_EU(d, shape) \
     (((d) >= 2 && ((shape) & kShapeWide) != 0) ? RT_WPE_WIDE \
-     : (d) == 2 ? RT_WPE2 : ((d) >= 2 ? RT_WPE_DEEP : ((d) == 0 ? RT_WPE0 : 1)))
+     : (d) == 2 ? RT_WPE2 : ((d) >= 2 ? RT_WPE_DEEP : ((d) == 0 ? ((shape) == 0 ? RT_WPE0_GENERAL : RT_WPE0) : 1)))
 #endif
 #ifndef RT_WPE0_MC
 // depth-0 Monte-Carlo kernel (config 5): 6 waves, 80 VGPRs + 16 B scratch:
@@ -1732,10 +1747,17 @@ struct Pixel {
     int x, local_row, y;
     bool active;
 };
+template <int kLaunch = 0>
 __device__ __forceinline__ Pixel wave_pixel(const LaunchParams &p, int wx, int wy) {
     const int lane = threadIdx.x & 63;
     Pixel px;
     px.x = wx * 8 + (lane & 7);
+    if constexpr ((kLaunch & kLaunchPlain) != 0) {  // rows 0..height of the frame, one slice
+        px.local_row = wy * 8 + (lane >> 3);
+        px.active = px.x < p.width && px.local_row < p.height;
+        px.y = px.active ? px.local_row : wy * 8;
+        return px;
+    }
     px.local_row = p.slice_begin + wy * 8 + (lane >> 3);
     px.active = px.x < p.width && px.local_row < p.slice_begin + p.slice_rows;
     px.y = output_row(p, px.active ? px.local_row : p.slice_begin + wy * 8);
@@ -1744,8 +1766,11 @@ __device__ __forceinline__ Pixel wave_pixel(const LaunchParams &p, int wx, int w
 
 // Camera ray through pixel (x, y) offset by (jx, jy) (:377-392); jx = jy = 0
 // for the reference's one ray per pixel (float(x - hw) + 0.0f is exact).
+template <int kLaunch = 0>
 __device__ __forceinline__ Ray camera_ray(const LaunchParams &p, const FrameView &V, int x, int y, float jx,
                                           float jy) {
+    // (a plain launch: at least 2 x 2 pixels and the host's short-division proof hold)
+    constexpr bool kPlain = (kLaunch & kLaunchPlain) != 0;
     const int hw = p.width / 2, hh = p.height / 2;
     const float *M = V.unproj;  // column-major
     // x - hw + jx is +0 or a multiple of 2^-24 of magnitude <= 2^16: the
@@ -1753,7 +1778,7 @@ __device__ __forceinline__ Ray camera_ray(const LaunchParams &p, const FrameView
     // one (a 1-pixel-wide or -high frame divides by 0: IEEE path)
     const float nx = static_cast<float>(x - hw) + jx, ny = static_cast<float>(y - hh) + jy;
     float vx, vy;
-    if (hw > 0 && hh > 0) {
+    if (kPlain || (hw > 0 && hh > 0)) {
         vx = div_r(nx, rcp_refined(static_cast<float>(hw)));
         vy = div_r(ny, rcp_refined(static_cast<float>(hh)));
     } else {
@@ -1770,7 +1795,7 @@ __device__ __forceinline__ Ray camera_ray(const LaunchParams &p, const FrameView
     // slower, config 2 38.9 -> 40.3 us per frame: the check is now made once
     // per launch on the host and read as a uniform argument)
     v3 s3, e3;
-    if (p.cam_short) {
+    if (kPlain || p.cam_short) {
         // the host proved every numerator +0 or in [2^-60, 2^60] and every w
         // in [2^-20, 2^20] for this frame (rt_scene.cpp camera_short_divisions):
         // one refined reciprocal per w and one correction per quotient, the
@@ -1792,7 +1817,7 @@ __device__ __forceinline__ Ray camera_ray(const LaunchParams &p, const FrameView
 // One 8x8 wave tile (wx, wy) of view z: lane l renders pixel (8 wx + l % 8,
 // 8 wy + l / 8). `pre`: the lane's camera ray, already computed (the tiled
 // path computes it while the scene is staged), or nullptr.
-template <int kDepth, bool kAccum, int kShape>
+template <int kDepth, bool kAccum, int kShape, int kLaunch = 0>
 __device__ __forceinline__ void render_wave_tile(const LaunchParams &p, Scene S, const FrameView &V, int wx, int wy,
                                                  int z, const Pixel &px, const Ray &pre, bool have_pre) {
     S.cull = V.cull;
@@ -1834,12 +1859,15 @@ __device__ __forceinline__ void render_wave_tile(const LaunchParams &p, Scene S,
     if (!wave_any(px.active)) return;
     const int x = px.x, y = px.y, local_row = px.local_row;
     const bool active = px.active;
-    const int lr0 = p.slice_begin + wy * 8;
+    constexpr bool kPlain = (kLaunch & kLaunchPlain) != 0;
+    static_assert(!kPlain || (kDepth == 0 && !kAccum && (kShape & kShapeMaskBytes) != 0),
+                  "plain launches: the depth-0 shaped kernels, no accumulation");
+    const int lr0 = (kPlain ? 0 : p.slice_begin) + wy * 8;
     S.tx0 = wx * 8;
     S.tx1 = S.tx0 + 7;
-    if (p.n_shards <= 0 || (p.block_rows % 8 == 0 && lr0 % 8 == 0)) {
+    if (kPlain || p.n_shards <= 0 || (p.block_rows % 8 == 0 && lr0 % 8 == 0)) {
         // the wave's 8 local rows lie in one block: 8 consecutive frame rows
-        S.ty0 = output_row(p, lr0);
+        S.ty0 = output_row<kLaunch>(p, lr0);
         S.ty1 = S.ty0 + 7;
     } else {
         S.ty0 = INT_MAX;
@@ -1854,7 +1882,7 @@ __device__ __forceinline__ void render_wave_tile(const LaunchParams &p, Scene S,
     const uint32_t idx = static_cast<uint32_t>(local_row) * static_cast<uint32_t>(p.width) + static_cast<uint32_t>(x);
 
     if constexpr (!kAccum) {
-        const Ray ray = have_pre ? pre : camera_ray(p, V, x, y, 0.0f, 0.0f);
+        const Ray ray = have_pre ? pre : camera_ray<kLaunch>(p, V, x, y, 0.0f, 0.0f);
 #if defined(RT_ABLATE_RAYGEN)
         (void)ray;
         const v3 col = mk(float(x), float(y), 0.0f);
@@ -1869,7 +1897,7 @@ __device__ __forceinline__ void render_wave_tile(const LaunchParams &p, Scene S,
         const v3 col = trace0(S, ray, active);
 #endif
         RT_CYC_AFTER(kCycStore, col.x);
-        if (active) store_pixel(p, z, idx, col);
+        if (active) store_pixel<kLaunch>(p, z, idx, col);
     } else {
         const uint32_t pixel = static_cast<uint32_t>(y) * static_cast<uint32_t>(p.width) + static_cast<uint32_t>(x);
         v3 acc = mk(0.0f, 0.0f, 0.0f);
@@ -1920,8 +1948,10 @@ constexpr bool kQueuedDepth(int depth) { return depth >= 2; }
 // frame constants come from the context's device buffer (p.views_dev,
 // p.consts_dev) instead of the kernel arguments; the view is read through
 // the constant address space (scalar loads, as the kernel arguments are).
-template <int kDepth, bool kAccum, bool kDev = false, int kShape = 0>
+// kLaunch: the launch's own uniform answers as constants (kLaunchPlain).
+template <int kDepth, bool kAccum, bool kDev = false, int kShape = 0, int kLaunch = 0>
 __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchParams p) {
+    constexpr bool kPlain = (kLaunch & kLaunchPlain) != 0;
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
     // A wave in its prologue (kernel arguments, the scene into LDS, the
     // barrier) issues ahead of the older waves of its SIMD, which the arbiter
@@ -1971,17 +2001,17 @@ __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchPar
     float4 *box_cam = reinterpret_cast<float4 *>(sph_px + p.n_spheres);
     const int own_wx = static_cast<int>(blockIdx.x) * kWavesX + wave % kWavesX;
     const int own_wy = static_cast<int>(blockIdx.y) * kWavesY + wave / kWavesX;
-    const Pixel own = wave_pixel(p, own_wx, own_wy);
+    const Pixel own = wave_pixel<kLaunch>(p, own_wx, own_wy);
     RT_PHASE_AFTER(14, own.y);
     Ray own_ray{mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f)};
-    if (!queued && !kAccum) own_ray = camera_ray(p, V, own.x, own.y, 0.0f, 0.0f);
+    if (!queued && !kAccum) own_ray = camera_ray<kLaunch>(p, V, own.x, own.y, 0.0f, 0.0f);
     RT_PHASE_AFTER(15, own_ray.dir.x + own_ray.dir.y + own_ray.dir.z);
     RT_PHASE(10);
     if (tid < p.blob_units) lds[tid] = first;
     RT_PHASE(11);
     for (int i = tid + kThreads; i < p.blob_units; i += kThreads) lds[i] = blob[i];
     const int view_units = (kLean ? 1 : 2) * p.n_spheres + p.n_boxes;
-    if (p.n_frame_consts > 0) {
+    if (kPlain || p.n_frame_consts > 0) {  // (a plain launch carries the host's records)
         if (tid < keep) views[tid] = fc;
         if (kLean) {
             for (int i = tid + keep; i < n_staged * keep; i += kThreads) {
@@ -2047,7 +2077,7 @@ __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchPar
     S.nl = p.n_lights;
     S.nm = p.n_mats;
     const int wtx = (p.width + 7) / 8;
-    const int view_tiles = wtx * ((p.slice_rows + 7) / 8);
+    const int view_tiles = wtx * (((kPlain ? p.height : p.slice_rows) + 7) / 8);
     const int total = queued ? view_tiles * p.n_views : 1;
     const int g = static_cast<int>(blockIdx.x) * (kThreads / 64) + wave;  // global wave
     const int n_waves = static_cast<int>(gridDim.x) * (kThreads / 64);
@@ -2073,8 +2103,9 @@ __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchPar
             St.sph_px = reinterpret_cast<const int4 *>(c + (kLean ? 0 : p.n_spheres));
             St.box_cam = reinterpret_cast<const float4 *>(St.sph_px + p.n_spheres);
         }
-        render_wave_tile<kDepth, kAccum, kShape>(p, St, queued ? p.view[zt] : V, wx, wy, zt,
-                                              queued ? wave_pixel(p, wx, wy) : own, own_ray, !(queued || kAccum));
+        render_wave_tile<kDepth, kAccum, kShape, kLaunch>(p, St, queued ? p.view[zt] : V, wx, wy, zt,
+                                                       queued ? wave_pixel<kLaunch>(p, wx, wy) : own, own_ray,
+                                                       !(queued || kAccum));
         t = queued ? (q_waves + __builtin_amdgcn_readfirstlane(nxt)) * kQueues + q : total;
     }
     RT_PHASE(7);
@@ -2146,11 +2177,11 @@ int queued_views_for(const void *fn, const LaunchParams &p) {
     return n;
 }
 
-template <int kDepth, bool kAccum, bool kDev = false, int kShape = 0>
+template <int kDepth, bool kAccum, bool kDev = false, int kShape = 0, int kLaunch = 0>
 hipError_t launch_kernel(LaunchParams &p, hipStream_t stream) {
     p.lean_views = kLeanViews(kShape) ? 1 : 0;
     size_t lds = lds_bytes(p);
-    const void *fn = reinterpret_cast<const void *>(&render_kernel<kDepth, kAccum, kDev, kShape>);
+    const void *fn = reinterpret_cast<const void *>(&render_kernel<kDepth, kAccum, kDev, kShape, kLaunch>);
     dim3 grid((p.width + kTileX - 1) / kTileX, (p.slice_rows + kTileY - 1) / kTileY, p.n_views);
     const int wave_tiles = ((p.width + 7) / 8) * ((p.slice_rows + 7) / 8) * p.n_views;
     const int resident = p.n_cu > 0 ? groups_per_cu(fn, lds) * p.n_cu : 0;
@@ -2168,21 +2199,31 @@ hipError_t launch_kernel(LaunchParams &p, hipStream_t stream) {
     } else {
         p.sched = nullptr;
     }
-    hipLaunchKernelGGL((render_kernel<kDepth, kAccum, kDev, kShape>), grid, dim3(kThreads), lds, stream, p);
+    hipLaunchKernelGGL((render_kernel<kDepth, kAccum, kDev, kShape, kLaunch>), grid, dim3(kThreads), lds, stream, p);
     return hipGetLastError();
 }
 
 // The depth-0 kernels in the scene's shape (scene_shape): 2-, 4- or 8-byte
 // LDS masks, one box or several; anything else runs the general kernel.
+// A shaped kernel also takes the launch's shape (launch_shape) where one
+// applies: the plain launch, never with accumulation.
+template <bool kAccum, bool kDev, int kShape>
+hipError_t launch_shaped0(LaunchParams &p, hipStream_t stream) {
+    if constexpr (!kAccum) {
+        if ((launch_shape(p, 0) & kLaunchPlain) != 0)
+            return launch_kernel<0, false, kDev, kShape, kLaunchPlain>(p, stream);
+    }
+    return launch_kernel<0, kAccum, kDev, kShape>(p, stream);
+}
 template <bool kAccum, bool kDev>
 hipError_t launch_depth0(LaunchParams &p, hipStream_t stream) {
     switch (scene_shape(p, 0)) {
-        case 2: return launch_kernel<0, kAccum, kDev, 2>(p, stream);
-        case 4: return launch_kernel<0, kAccum, kDev, 4>(p, stream);
-        case 8: return launch_kernel<0, kAccum, kDev, 8>(p, stream);
-        case 2 | kShapeRoom: return launch_kernel<0, kAccum, kDev, 2 | kShapeRoom>(p, stream);
-        case 4 | kShapeRoom: return launch_kernel<0, kAccum, kDev, 4 | kShapeRoom>(p, stream);
-        case 8 | kShapeRoom: return launch_kernel<0, kAccum, kDev, 8 | kShapeRoom>(p, stream);
+        case 2: return launch_shaped0<kAccum, kDev, 2>(p, stream);
+        case 4: return launch_shaped0<kAccum, kDev, 4>(p, stream);
+        case 8: return launch_shaped0<kAccum, kDev, 8>(p, stream);
+        case 2 | kShapeRoom: return launch_shaped0<kAccum, kDev, 2 | kShapeRoom>(p, stream);
+        case 4 | kShapeRoom: return launch_shaped0<kAccum, kDev, 4 | kShapeRoom>(p, stream);
+        case 8 | kShapeRoom: return launch_shaped0<kAccum, kDev, 8 | kShapeRoom>(p, stream);
         default: return launch_kernel<0, kAccum, kDev, 0>(p, stream);
     }
 }
@@ -2230,6 +2271,16 @@ int scene_shape(const LaunchParams &p, int max_depth) {
         return kShapeWide | box;
     }
     return 0;
+}
+
+int launch_shape(const LaunchParams &p, int max_depth) {
+    if (!p.shape_launch || max_depth != 0 || p.spp > 0) return 0;  // (RT_OPT_LAUNCH_SHAPES 0, deeper, Monte-Carlo)
+    const int slice_rows = p.slice_rows > 0 ? p.slice_rows : p.n_rows;  // (launch_render: 0 = the whole launch)
+    const int slice_begin = p.slice_rows > 0 ? p.slice_begin : 0;
+    const bool plain = p.n_shards <= 0 && p.row_begin == 0 && p.n_rows == p.height && slice_begin == 0 &&
+                       slice_rows == p.n_rows && p.out_format == RT_OUTPUT_RGBA32F && p.cam_short == 1 &&
+                       p.n_frame_consts > 0 && p.width >= 2 && p.height >= 2;
+    return plain ? kLaunchPlain : 0;
 }
 
 size_t lds_bytes(const LaunchParams &p) {
@@ -2320,7 +2371,9 @@ hipError_t allow_large_lds(size_t bytes) {
                   reinterpret_cast<const void *>(&render_kernel<d, true>)
 #define RT_SHAPES(k) reinterpret_cast<const void *>(&render_kernel<0, false, false, k>), \
                      reinterpret_cast<const void *>(&render_kernel<0, true, false, k>),  \
-                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k>)
+                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k>),  \
+                     reinterpret_cast<const void *>(&render_kernel<0, false, false, k, kLaunchPlain>), \
+                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k, kLaunchPlain>)
 #define RT_WIDE(d) reinterpret_cast<const void *>(&render_kernel<d, false, false, kShapeWide>), \
                    reinterpret_cast<const void *>(&render_kernel<d, false, false, kShapeWide | kShapeRoom>)
     const void *fns[] = {RT_KFN(0), RT_KFN(1), RT_KFN(2), RT_KFN(3), RT_KFN(4),

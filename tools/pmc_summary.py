@@ -22,7 +22,13 @@ With --frames N every figure is the sum over the kept dispatches divided by
 the N frames the profiled bench run rendered, i.e. per frame; without it,
 per dispatch.
 
-usage: python tools/pmc_summary.py SRC DST [FRAMES_PER_LAUNCH] [WORKLOAD] [--frames N] [--skip N]
+With --issue the three further passes of PROFILE_ISSUE=1 tools/profile.sh
+(pmc_mix, pmc_ifetch, pmc_scalar) are summarised too, as `issue_supply`: the
+instruction mix per wave (one 8 x 8 wave tile per wave in a tiled launch),
+VALU lane utilisation, and the instruction-cache and scalar-cache requests
+and hit rates, each figure normalised by the SQ_WAVES of its own pass.
+
+usage: python tools/pmc_summary.py SRC DST [FRAMES_PER_LAUNCH] [WORKLOAD] [--frames N] [--skip N] [--issue]
 (FRAMES_PER_LAUNCH: views per render launch of the profiled bench run, default 8;
 WORKLOAD: bench.py --workload of the run, default config2). Writes
 profiles/pmc_<WORKLOAD>_latest.json (bench.py reads it) and, for config2,
@@ -39,6 +45,7 @@ from collections import defaultdict
 KERNELS = ("render_kernel",)
 SHORT_FRACTION = 0.6  # a kept dispatch lasts at least this share of its group's median
 PASSES = ("pmc_write", "pmc_fetch", "pmc_sq", "pmc_cyc", "pmc_l2", "pmc_lds")
+ISSUE_PASSES = ("pmc_mix", "pmc_ifetch", "pmc_scalar")  # --issue (PROFILE_ISSUE=1 tools/profile.sh)
 
 
 def ours(name):
@@ -115,7 +122,30 @@ def counters(src, name, skip=0):
     return {k: list(v.values()) for k, v in agg.items()}, sel
 
 
-def summarise(src, workload="config2", frames_per_launch=8, frames=None, skip=0):
+def issue_supply(passes):
+    """Per-wave figures of the --issue passes ({pass: {counter: [per-dispatch
+    values]}}): every counter of a pass divided by that pass's SQ_WAVES."""
+    out = {}
+    for name in ISSUE_PASSES:
+        vals = passes.get(name) or {}
+        waves = sum(vals.get("SQ_WAVES", []))
+        if not waves:
+            continue
+        for cname, v in vals.items():
+            if cname != "SQ_WAVES":
+                out[cname.lower() + "_per_wave"] = sum(v) / waves
+    def ratio(a, b):
+        return out[a] / out[b] if out.get(a) is not None and out.get(b) else None
+    # lanes active per VALU instruction, of 64 (SQ_THREAD_CYCLES_VALU counts
+    # one per active lane per instruction on gfx950: 63.6 for config 2's
+    # full tiles)
+    out["valu_lanes_active"] = ratio("sq_thread_cycles_valu_per_wave", "sq_insts_valu_per_wave")
+    out["icache_hit_rate"] = ratio("sqc_icache_hits_per_wave", "sqc_icache_req_per_wave")
+    out["scalar_cache_hit_rate"] = ratio("sqc_dcache_hits_per_wave", "sqc_dcache_req_per_wave")
+    return out
+
+
+def summarise(src, workload="config2", frames_per_launch=8, frames=None, skip=0, issue=False):
     def per_launch(vals):
         if not vals:
             return None
@@ -193,6 +223,14 @@ def summarise(src, workload="config2", frames_per_launch=8, frames=None, skip=0)
         # wave64 VALU issue: 2 cycles per instruction per SIMD, 1024 SIMDs
         clk = out.get("effective_clock_ghz") or 2.4
         out["valu_issue_utilisation"] = out["sq_insts_valu_per_launch"] * 2 / (1024 * clk * out["avg_kernel_ns"])
+    if issue:
+        extra = {}
+        for name in ISSUE_PASSES:
+            vals, sel = counters(src, name, skip)
+            extra[name] = vals
+            if sel is not None:
+                selection[name] = sel
+        out["issue_supply"] = issue_supply(extra)
     if out["l2_hit_per_launch"] is not None and out["l2_miss_per_launch"] is not None:
         tot = out["l2_hit_per_launch"] + out["l2_miss_per_launch"]
         out["l2_hit_rate"] = out["l2_hit_per_launch"] / tot if tot else None
@@ -207,6 +245,9 @@ def summarise(src, workload="config2", frames_per_launch=8, frames=None, skip=0)
 def main(argv):
     argv = list(argv)
     frames = skip = None
+    issue = "--issue" in argv
+    if issue:
+        argv.remove("--issue")
     for flag in ("--frames", "--skip"):
         if flag in argv:
             i = argv.index(flag)
@@ -219,7 +260,7 @@ def main(argv):
     src, dst = argv[0], argv[1]
     frames_per_launch = int(argv[2]) if len(argv) > 2 else 8
     workload = argv[3] if len(argv) > 3 else "config2"
-    out = summarise(src, workload, frames_per_launch, frames, skip or 0)
+    out = summarise(src, workload, frames_per_launch, frames, skip or 0, issue)
     os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)
     with open(dst + "_pmc.json", "w") as fo:
         json.dump(out, fo, indent=1)

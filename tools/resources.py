@@ -42,14 +42,18 @@ def lib_path(spec):
 
 
 def kernel_name(mangled):
-    """render_kernel<D, MC, DEV[, SHAPE]> from the mangled name (SHAPE: the
-    scene shapes, rt_internal.h kShapeRoom), else the mangled name."""
-    m = re.search(r"render_kernelILi(\d)ELb([01])ELb([01])E(?:Li(\d+)E)?", mangled)
+    """render_kernel<D, MC, DEV[, SHAPE[, LAUNCH]]> from the mangled name
+    (SHAPE: the scene shapes, rt_internal.h kShapeRoom; LAUNCH: the launch
+    shapes, kLaunchPlain; each left out when 0), else the mangled name."""
+    m = re.search(r"render_kernelILi(\d)ELb([01])ELb([01])E(?:Li(\d+)E)?(?:Li(\d+)E)?", mangled)
     if m:
         name = "render_kernel<%s,%s,%s" % (m.group(1), "true" if m.group(2) == "1" else "false",
                                            "true" if m.group(3) == "1" else "false")
-        if m.group(4) and m.group(4) != "0":
-            name += ",%s" % m.group(4)
+        shape, launch = m.group(4) or "0", m.group(5) or "0"
+        if shape != "0" or launch != "0":
+            name += ",%s" % shape
+        if launch != "0":
+            name += ",%s" % launch
         return name + ">"
     return mangled
 
@@ -109,8 +113,9 @@ def gate(base, variant, kernels=None):
 
 # DESIGN.md §3's occupancy table: (row label, kernel) in the order it lists them
 TABLE = [
-    ("depth 0, config 2 (room, 2-B masks, > 8 views: device views)", "render_kernel<0,false,true,18>"),
-    ("depth 0, the shipped scene (2-B masks, 4 boxes, device views)", "render_kernel<0,false,true,2>"),
+    ("depth 0, config 2 (room, 2-B masks, > 8 views: device views, plain launch)", "render_kernel<0,false,true,18,1>"),
+    ("depth 0, config 2, any other launch shape", "render_kernel<0,false,true,18>"),
+    ("depth 0, the shipped scene (2-B masks, 4 boxes, device views, plain launch)", "render_kernel<0,false,true,2,1>"),
     ("depth 0, Monte-Carlo, config 5", "render_kernel<0,true,false,18>"),
     ("depth 0, general", "render_kernel<0,false,false>"),
     ("depth 0, Monte-Carlo, general", "render_kernel<0,true,false>"),
