@@ -357,6 +357,18 @@ int rt_multi_last_ms(rt_multi *m, float *kernel_ms, float *gather_ms, float *ass
  * mapping, surface format, division form) is made at run time. 0: every
  * render reads them at run time. Output is identical. */
 #define RT_OPT_LAUNCH_SHAPES 9
+/* RT_OPT_PERSISTENT0 (default 1): how a depth-0 rt_render_batch of more than
+ * 8 views of one scene that takes the plain launch shape (RT_OPT_LAUNCH_SHAPES)
+ * is distributed. 1: automatic — a grid of as many work-groups as are
+ * resident at once, each staging the scene once, whose waves take chunks of
+ * 8x8-pixel tiles from queues until the launch is done, when the launch has
+ * at least 192 tiles per resident wave (49 frames of 1920x1080 on an
+ * MI355X: below that the tiled launch measured faster); otherwise one
+ * work-group per 16x16 tile. 0: always one work-group per tile. k >= 8: the resident grid whatever
+ * the launch's size, of at most k work-groups (a development hook: small
+ * frames then run the queue loop). Other values are refused. Output is
+ * identical. */
+#define RT_OPT_PERSISTENT0 10
 /* (option 6, a tolerance tier that summed the recursion's colours forward
  * instead of mixing them on the way back up, measured even with the exact
  * walk and was removed: DESIGN.md §3.) */

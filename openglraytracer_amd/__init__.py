@@ -243,6 +243,14 @@ class Context:
         (include/rt.h). Output identical either way."""
         _check(lib().rt_context_set(self._h, abi.RT_OPT_LAUNCH_SHAPES, 1 if on else 0))
 
+    def set_persistent0(self, value):
+        """RT_OPT_PERSISTENT0: the distribution of a plain depth-0 batch of
+        more than 8 views of one scene (include/rt.h). 1: the resident grid
+        when the launch is large enough (default); 0: one work-group per
+        tile; k >= 8: the resident grid of at most k work-groups whatever the
+        launch's size. Output identical either way."""
+        _check(lib().rt_context_set(self._h, abi.RT_OPT_PERSISTENT0, int(value)))
+
     def set_output(self, fmt):
         """RT_OPT_OUTPUT: abi.RT_OUTPUT_RGBA32F (float4 per pixel),
         abi.RT_OUTPUT_RGBA8 (the shipped GL_RGBA8 surface, 4 bytes per pixel)

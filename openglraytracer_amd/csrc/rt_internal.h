@@ -264,7 +264,13 @@ struct LaunchParams {
     // host only: RT_OPT_LAUNCH_SHAPES, the depth-0 shaped kernels may take the
     // launch's shape (launch_shape)
     int32_t shape_launch;
+    // host only: RT_OPT_PERSISTENT0 (0 off, 1 automatic, k >= 8: forced, at
+    // most k work-groups; persistent_groups), 0 too when a view of the batch
+    // carries a scene blob of its own (rt_render_batch_scenes). (In the
+    // block's tail padding: the argument block keeps its size.)
+    int32_t persistent0;
 };
+static_assert(sizeof(LaunchParams) == 5808, "kernel argument block: the hidden arguments' offsets");
 // ROCm passes kernel arguments above 4 KiB (an 8 KB argument block checked on
 // MI355X); this block stays under 6 KiB.
 static_assert(sizeof(LaunchParams) <= 6144, "kernel argument block");
@@ -292,7 +298,39 @@ int scene_shape(const LaunchParams &p, int max_depth);
 // host (launch_shape) from the parameters alone; RT_OPT_LAUNCH_SHAPES 0
 // (LaunchParams::shape_launch) forces 0.
 constexpr int kLaunchPlain = 1;
-int launch_shape(const LaunchParams &p, int max_depth);
+// kLaunchPersistent (only with kLaunchPlain, on the device-view kernels): the
+// resident-grid distribution of a depth-0 batch of one scene (rt_kernel.hip,
+// "Work distribution"). Needs the kernel's resident work-groups, so
+// launch_shape reports it only for a launch whose `resident` is known.
+constexpr int kLaunchPersistent = 2;
+int launch_shape(const LaunchParams &p, int max_depth, int resident = 0);
+// Wave tiles a persistent wave takes per dequeue (kChunk0 consecutive items,
+// view-major): 256 frames of 1080p need about 1,250 tiles per microsecond
+// and one counter serves about 88 dequeues per microsecond, so the 32 heads
+// at 8 tiles each run at a sixth of their ceiling.
+#ifndef RT_CHUNK0
+#define RT_CHUNK0 8
+#endif
+constexpr int kChunk0 = RT_CHUNK0;
+// The launch's last kTailTiles0 tiles per wave of the grid are dealt one tile
+// per dequeue: a wave tile takes about 6 us of a wave's time with 8 waves on
+// its SIMD, so whole chunks alone left a tail of up to 50 us (measured: 35 us
+// more per launch than the tiled launch's), which the waves that finish
+// their last chunk early now fill tile by tile.
+#ifndef RT_TAIL_TILES0
+#define RT_TAIL_TILES0 4
+#endif
+constexpr int kTailTiles0 = RT_TAIL_TILES0;
+// Automatic persistence (RT_OPT_PERSISTENT0 1) from this many wave tiles per
+// resident wave. Measured on config 2 at 1080p, tiled -> persistent per
+// launch: 9 views (36 tiles per wave) 271 -> 304 us, 16: 455 -> 474, 32:
+// 879 -> 885, 48 (190 per wave): 1300 -> 1287, 64: 1720 -> 1686, 128:
+// 3390 -> 3280, 256: 6.66 -> 6.37 ms. The persistent launch costs about 43 us
+// more per launch and 4.6 % less per view, so it pays from about 40 views.
+constexpr int kPersistentMinTilesPerWave = 192;
+// Work-groups of the persistent grid for a plain depth-0 launch on a kernel
+// with `resident` resident work-groups on the device, 0: the tiled launch.
+int persistent_groups(const LaunchParams &p, int resident);
 // Lean views (LaunchParams::lean_views): the wide-shape kernels.
 constexpr bool kLeanViews(int shape) { return (shape & kShapeWide) != 0; }
 // 16-B records of one view's per-frame constants in LDS: the spheres' camera
@@ -411,6 +449,7 @@ struct rt_context {
     int origin_lists = 1;  // RT_OPT_ORIGIN_LISTS
     int scene_shapes = 1;  // RT_OPT_SCENE_SHAPES
     int launch_shapes = 1;  // RT_OPT_LAUNCH_SHAPES
+    int persistent0 = 1;  // RT_OPT_PERSISTENT0
     // device-side view batches (> kMaxViews views): per slot a device buffer,
     // its pinned host staging and an event after the last launch that read it
     void *batch_dev[rtamd::kBatchSlots] = {};
@@ -426,6 +465,7 @@ struct rt_context {
     // than kSchedSlots queued launches in flight never share counters
     hipEvent_t sched_done[rtamd::kSchedSlots] = {};
     bool sched_used[rtamd::kSchedSlots] = {};
+    bool last_queued = false;   // the last launch used its slot (rt_debug_last_queued)
     std::vector<struct rt_scene *> scenes;  // live scenes (detached by rt_destroy)
 };
 

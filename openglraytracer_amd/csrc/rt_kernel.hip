@@ -1941,18 +1941,182 @@ __device__ __forceinline__ void render_wave_tile(const LaunchParams &p, Scene S,
 // recursive depths); depth 0 / 1 keep the tiled kernel, whose body the
 // compiler schedules with fewer registers (config 2: 70 vs 81 VGPRs).
 // (r02: queued from depth 0, 64 VGPRs + 84 B scratch: config 2 single frame
-// 52 -> 67 us, 8-frame launches, tiled either way, 41.5 -> 50.6 us per frame)
+// 52 -> 67 us, 8-frame launches, tiled either way, 41.5 -> 50.6 us per frame.
+// Depth-0 batches of 49 or more 1080p frames of one scene now take the
+// persistent distribution below, which re-reads its arguments per tile and
+// so fits 64 VGPRs without scratch: 26.0 -> 24.9 us per frame at 256.)
 constexpr bool kQueuedDepth(int depth) { return depth >= 2; }
+
+//  * Persistent (kLaunchPersistent: a plain depth-0 batch of more than
+//    kMaxViews views of one scene, p.sched set; persistent_groups decides):
+//    the queued grid for the depth-0 shaped kernels. A work-group stages the
+//    scene once (one barrier); after it no wave waits for another. The items
+//    are the launch's wave tiles, view-major (item t = tile t % T of view
+//    t / T, a view's tiles row by row), dealt in chunks of kChunk0
+//    consecutive items, the last kTailTiles0 per wave one by one (chunks
+//    of one): chunk c belongs to queue c % kQueues, wave g starts
+//    with chunk g and then takes its queue's next chunk from the atomic head,
+//    fetched one chunk ahead. Division by the frame's tile counts happens
+//    once per chunk; inside it the tile steps to its right-hand neighbour. The
+//    view comes from p.views_dev by scalar loads, and its frame constants
+//    into a slot of the wave's own in LDS (after the scene: kThreads / 64
+//    slots of n_frame_consts records), refilled by the wave itself when its
+//    view changes — LDS operations of one wave complete in order, so the
+//    refill needs only a compiler fence. The trip count is bounded by the
+//    launch's chunks; the last wave of a queue to run dry resets its counters.
+//    Registers: only the item, the chunk's end, the tile's coordinates, the
+//    slot's view and the fetched head stay live across a tile. Every tile
+//    reads the launch's arguments again, as a tiled work-group does (through
+//    a pointer the compiler cannot see through, so nothing derived from them
+//    is hoisted out of the loop and held in registers across the body: hoisted,
+//    the kernel took 28-44 B of scratch per lane and 43 spilled SGPRs).
+using LaunchArgs = const __attribute__((address_space(4))) LaunchParams *;
+__device__ __forceinline__ const LaunchParams &launch_args() {
+    LaunchArgs a = (LaunchArgs)__builtin_amdgcn_kernarg_segment_ptr();  // (the kernel's one argument)
+    asm volatile("" : "+s"(a));
+    return *(const LaunchParams *)a;
+}
+// The wave's slot of view records in LDS, after the scene.
+__device__ __forceinline__ float4 *persistent_slot(const LaunchParams &p, float4 *lds) {
+    return lds + p.blob_units + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * p.n_frame_consts;
+}
+// View z's records into the wave's slot. The fences order the refill between
+// the previous tile's reads and the next tile's: one wave, in-order LDS.
+__device__ __forceinline__ void persistent_refill(const LaunchParams &p, float4 *lds, int z) {
+    float4 *const slot = persistent_slot(p, lds);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));  // (its byte offset is not kept in a register across the tiles)
+    for (int i = lane; i < p.n_frame_consts; i += 64) slot[i] = p.consts_dev[z * p.n_frame_consts + i];
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+// One item: wave tile (wx, wy) of view z, the view's records in the slot.
+template <int kShape, int kLaunch>
+__device__ __forceinline__ void persistent_tile(const LaunchParams &p, float4 *lds, int z, int wx, int wy) {
+    const float4 *blob = static_cast<const float4 *>(p.scene);
+    float4 *const slot = persistent_slot(p, lds);
+    Scene S;
+    S.sph = lds + p.off_spheres;
+    S.smeta = reinterpret_cast<const int4 *>(lds + p.off_smeta);
+    S.sph_cam = slot;
+    S.sph_px = reinterpret_cast<const int4 *>(slot + p.n_spheres);
+    S.box = reinterpret_cast<const BoxRec *>(lds + p.off_boxes);
+    S.box_cam = slot + 2 * p.n_spheres;
+    S.mat = reinterpret_cast<const MatRec *>(lds + p.off_mats);
+    S.light = reinterpret_cast<const LightRec *>(lds + p.off_lights);
+    S.lm = reinterpret_cast<const LightMatRec *>(lds + p.off_lightmat);
+    S.bvh = lds + p.off_bvh;
+    S.blink = reinterpret_cast<const uint32_t *>(lds + p.off_blink);
+    S.cone = nullptr;  // (a depth-0 mask shape: render_wave_tile sets the rest of the shape)
+    S.dmask = reinterpret_cast<const char *>(lds + p.off_dmask);
+    S.dmask_n = kShapeMaskTexels;
+    S.dmask_bytes = kShape & kShapeMaskBytes;
+    S.dmask_box = p.dmask_box;
+    S.cbplane = p.off_bplane >= 0 ? (const __attribute__((address_space(4))) float4 *)(blob + p.off_bplane) : nullptr;
+    S.gmask = nullptr;
+    S.gwords = 0;
+    S.glist = nullptr;
+    S.olist = nullptr;
+    S.cbox = (const __attribute__((address_space(4))) BoxRec *)(blob + p.off_boxes);
+    S.clight = (const __attribute__((address_space(4))) LightRec *)(blob + p.off_lights);
+#ifdef RT_UNIFORM_MAT
+    S.cmat = (const __attribute__((address_space(4))) MatRec *)(blob + p.off_mats);
+    S.clm = (const __attribute__((address_space(4))) LightMatRec *)(blob + p.off_lightmat);
+#endif
+    S.nbvh = 0;
+    S.ns = p.n_spheres;
+    S.nb = p.n_boxes;
+    S.nl = p.n_lights;
+    S.nm = p.n_mats;
+    const FrameView V = cload((const __attribute__((address_space(4))) FrameView *)(p.views_dev) + z);
+    const Ray none{mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f)};
+    render_wave_tile<0, false, kShape, kLaunch>(p, S, V, wx, wy, z, wave_pixel<kLaunch>(p, wx, wy), none, false);
+}
+template <int kShape, int kLaunch>
+__device__ __forceinline__ void render_persistent0(float4 *lds) {
+    static_assert((kLaunch & kLaunchPlain) != 0 && (kShape & kShapeMaskBytes) != 0, "plain shaped launches");
+    __builtin_amdgcn_s_setprio(1);
+    {
+        const LaunchParams &p = launch_args();
+        const float4 *blob = static_cast<const float4 *>(p.scene);
+        for (int i = threadIdx.x; i < p.blob_units; i += kThreads) lds[i] = blob[i];
+    }
+    __syncthreads();
+    __builtin_amdgcn_s_setprio(0);
+    // global wave g of queue q = g % kQueues, one of the queue's q_waves waves
+    const auto global_wave = [] {
+        return static_cast<int>(blockIdx.x) * (kThreads / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    };
+    const auto queue_waves = [](int q) {
+        return (static_cast<int>(gridDim.x) * (kThreads / 64) - q + kQueues - 1) / kQueues;
+    };
+    int held = -1;  // the view whose records the slot holds
+    int c = global_wave();
+    for (;;) {
+        int t, t_end, z, wx, wy;
+        {
+            const LaunchParams &p = launch_args();
+            const int wtx = (p.width + 7) / 8, view_tiles = wtx * ((p.height + 7) / 8);
+            const int total = view_tiles * p.n_views;  // (< 2^30: persistent_groups)
+            // the launch's last kTailTiles0 tiles per wave go out one at a
+            // time (the tail: else a chunk of a wave's time, 8 x 6 us)
+            const int tail_max = kTailTiles0 * static_cast<int>(gridDim.x) * (kThreads / 64);
+            const int body = (total - (total < tail_max ? total : tail_max)) / kChunk0;  // whole chunks
+            if (c >= body + (total - body * kChunk0)) break;
+            // the queue's next chunk, fetched a chunk ahead: the fetch waits
+            // together with the refill's load, then lives in a scalar register
+            const int q = global_wave() % kQueues;
+            int nxt = 0;
+            if ((threadIdx.x & 63) == 0) nxt = atomicAdd(p.sched + q * kQueueStride, 1);
+            t = c < body ? c * kChunk0 : body * kChunk0 + (c - body);
+            t_end = c < body ? t + kChunk0 : t + 1;
+            z = t / view_tiles;
+            const int r = t - z * view_tiles;
+            wy = r / wtx;
+            wx = r - wy * wtx;
+            if (z != held) persistent_refill(p, lds, z);
+            held = z;
+            c = (queue_waves(q) + __builtin_amdgcn_readfirstlane(nxt)) * kQueues + q;
+        }
+        for (; t < t_end; ++t) {
+            const LaunchParams &p = launch_args();
+            if (z != held) persistent_refill(p, lds, z);
+            held = z;
+            persistent_tile<kShape, kLaunch>(p, lds, z, wx, wy);
+            if (++wx == (p.width + 7) / 8) {
+                wx = 0;
+                if (++wy == (p.height + 7) / 8) {
+                    wy = 0;
+                    ++z;
+                }
+            }
+        }
+    }
+    const LaunchParams &p = launch_args();
+    const int q = global_wave() % kQueues;
+    if ((threadIdx.x & 63) == 0 && atomicAdd(p.sched + (kQueues + q) * kQueueStride, 1) == queue_waves(q) - 1) {
+        atomicExch(p.sched + q * kQueueStride, 0);  // every wave of the queue has made its last fetch
+        atomicExch(p.sched + (kQueues + q) * kQueueStride, 0);
+    }
+}
 
 // kDev: a batch of more than kMaxViews views (depth 0-1): view z and its
 // frame constants come from the context's device buffer (p.views_dev,
 // p.consts_dev) instead of the kernel arguments; the view is read through
 // the constant address space (scalar loads, as the kernel arguments are).
-// kLaunch: the launch's own uniform answers as constants (kLaunchPlain).
+// kLaunch: the launch's own uniform answers as constants (kLaunchPlain), and
+// the persistent distribution (kLaunchPersistent, render_persistent0).
 template <int kDepth, bool kAccum, bool kDev = false, int kShape = 0, int kLaunch = 0>
 __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchParams p) {
     constexpr bool kPlain = (kLaunch & kLaunchPlain) != 0;
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
+    if constexpr ((kLaunch & kLaunchPersistent) != 0) {
+        static_assert(kPlain && kDev && kDepth == 0 && !kAccum, "persistent: plain depth-0 device-view batches");
+        render_persistent0<kShape, kLaunch>(lds);
+        return;
+    }
     // A wave in its prologue (kernel arguments, the scene into LDS, the
     // barrier) issues ahead of the older waves of its SIMD, which the arbiter
     // otherwise favours by age; back to 0 after the barrier. Depth-0
@@ -2203,15 +2367,39 @@ hipError_t launch_kernel(LaunchParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// LDS of a persistent launch: the scene and one view's records per wave.
+size_t persistent_lds_bytes(const LaunchParams &p) {
+    return (static_cast<size_t>(p.blob_units) + static_cast<size_t>(kThreads / 64) * p.n_frame_consts) * sizeof(float4);
+}
+
 // The depth-0 kernels in the scene's shape (scene_shape): 2-, 4- or 8-byte
 // LDS masks, one box or several; anything else runs the general kernel.
 // A shaped kernel also takes the launch's shape (launch_shape) where one
 // applies: the plain launch, never with accumulation.
+// A plain device-view batch takes the persistent distribution where
+// persistent_groups says so: the grid is the kernel's resident work-groups
+// (or RT_OPT_PERSISTENT0's cap), the LDS the scene and a view's records per
+// wave.
 template <bool kAccum, bool kDev, int kShape>
 hipError_t launch_shaped0(LaunchParams &p, hipStream_t stream) {
     if constexpr (!kAccum) {
-        if ((launch_shape(p, 0) & kLaunchPlain) != 0)
+        if ((launch_shape(p, 0) & kLaunchPlain) != 0) {
+            if constexpr (kDev) {
+                constexpr int kPersistent = kLaunchPlain | kLaunchPersistent;
+                const size_t lds = persistent_lds_bytes(p);
+                if (p.persistent0 > 0 && p.sched && lds <= kMaxLds && p.n_cu > 0) {  // (else: no occupancy query)
+                    const void *fn = reinterpret_cast<const void *>(&render_kernel<0, false, true, kShape, kPersistent>);
+                    const int groups = persistent_groups(p, groups_per_cu(fn, lds) * p.n_cu);
+                    if (groups > 0) {
+                        p.lean_views = 0;
+                        hipLaunchKernelGGL((render_kernel<0, false, true, kShape, kPersistent>), dim3(groups),
+                                           dim3(kThreads), lds, stream, p);
+                        return hipGetLastError();
+                    }
+                }
+            }
             return launch_kernel<0, false, kDev, kShape, kLaunchPlain>(p, stream);
+        }
     }
     return launch_kernel<0, kAccum, kDev, kShape>(p, stream);
 }
@@ -2273,7 +2461,28 @@ int scene_shape(const LaunchParams &p, int max_depth) {
     return 0;
 }
 
-int launch_shape(const LaunchParams &p, int max_depth) {
+int persistent_groups(const LaunchParams &p, int resident) {
+#if defined(RT_STATS) || defined(RT_CYCLES) || defined(RT_PHASE_TRACE)
+    return 0;  // (the instrumented builds' probes live in the tiled prologue)
+#endif
+    // a plain batch of one scene in its scene's shape, views and records in
+    // device memory, counters to queue on
+    if (p.persistent0 <= 0 || (launch_shape(p, 0) & kLaunchPlain) == 0 || scene_shape(p, 0) == 0) return 0;
+    if (!p.views_dev || !p.consts_dev || p.n_views <= kMaxViews || !p.sched) return 0;
+    const bool forced = p.persistent0 >= 8;
+    const int groups = forced && p.persistent0 < resident ? p.persistent0 : resident;
+    const long long waves = static_cast<long long>(groups) * (kThreads / 64);
+    const long long tiles = static_cast<long long>((p.width + 7) / 8) * ((p.height + 7) / 8) * p.n_views;
+    if (waves < kQueues || tiles >= (1ll << 30)) return 0;  // (a queue without a wave; 32-bit item numbers)
+    if (!forced && tiles < kPersistentMinTilesPerWave * waves) return 0;
+    return groups;
+}
+
+int launch_shape(const LaunchParams &p, int max_depth, int resident) {
+    if (resident > 0) {
+        const int shape = launch_shape(p, max_depth);
+        return shape | (shape != 0 && persistent_groups(p, resident) > 0 ? kLaunchPersistent : 0);
+    }
     if (!p.shape_launch || max_depth != 0 || p.spp > 0) return 0;  // (RT_OPT_LAUNCH_SHAPES 0, deeper, Monte-Carlo)
     const int slice_rows = p.slice_rows > 0 ? p.slice_rows : p.n_rows;  // (launch_render: 0 = the whole launch)
     const int slice_begin = p.slice_rows > 0 ? p.slice_begin : 0;
@@ -2373,7 +2582,8 @@ hipError_t allow_large_lds(size_t bytes) {
                      reinterpret_cast<const void *>(&render_kernel<0, true, false, k>),  \
                      reinterpret_cast<const void *>(&render_kernel<0, false, true, k>),  \
                      reinterpret_cast<const void *>(&render_kernel<0, false, false, k, kLaunchPlain>), \
-                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k, kLaunchPlain>)
+                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k, kLaunchPlain>), \
+                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k, kLaunchPlain | kLaunchPersistent>)
 #define RT_WIDE(d) reinterpret_cast<const void *>(&render_kernel<d, false, false, kShapeWide>), \
                    reinterpret_cast<const void *>(&render_kernel<d, false, false, kShapeWide | kShapeRoom>)
     const void *fns[] = {RT_KFN(0), RT_KFN(1), RT_KFN(2), RT_KFN(3), RT_KFN(4),

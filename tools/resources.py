@@ -44,7 +44,8 @@ def lib_path(spec):
 def kernel_name(mangled):
     """render_kernel<D, MC, DEV[, SHAPE[, LAUNCH]]> from the mangled name
     (SHAPE: the scene shapes, rt_internal.h kShapeRoom; LAUNCH: the launch
-    shapes, kLaunchPlain; each left out when 0), else the mangled name."""
+    shapes, kLaunchPlain = 1, with kLaunchPersistent 3; each left out when
+    0), else the mangled name."""
     m = re.search(r"render_kernelILi(\d)ELb([01])ELb([01])E(?:Li(\d+)E)?(?:Li(\d+)E)?", mangled)
     if m:
         name = "render_kernel<%s,%s,%s" % (m.group(1), "true" if m.group(2) == "1" else "false",
@@ -114,6 +115,8 @@ def gate(base, variant, kernels=None):
 # DESIGN.md §3's occupancy table: (row label, kernel) in the order it lists them
 TABLE = [
     ("depth 0, config 2 (room, 2-B masks, > 8 views: device views, plain launch)", "render_kernel<0,false,true,18,1>"),
+    ("depth 0, config 2, 49 or more 1080p views per launch (plain launch, persistent grid)",
+     "render_kernel<0,false,true,18,3>"),
     ("depth 0, config 2, any other launch shape", "render_kernel<0,false,true,18>"),
     ("depth 0, the shipped scene (2-B masks, 4 boxes, device views, plain launch)", "render_kernel<0,false,true,2,1>"),
     ("depth 0, Monte-Carlo, config 5", "render_kernel<0,true,false,18>"),
