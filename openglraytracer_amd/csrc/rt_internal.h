@@ -304,29 +304,61 @@ constexpr int kLaunchPlain = 1;
 // launch_shape reports it only for a launch whose `resident` is known.
 constexpr int kLaunchPersistent = 2;
 int launch_shape(const LaunchParams &p, int max_depth, int resident = 0);
-// Wave tiles a persistent wave takes per dequeue (kChunk0 consecutive items,
-// view-major): 256 frames of 1080p need about 1,250 tiles per microsecond
-// and one counter serves about 88 dequeues per microsecond, so the 32 heads
-// at 8 tiles each run at a sixth of their ceiling.
+// Wave tiles a persistent wave takes per dequeue in the bulk of the launch
+// (kChunk0 consecutive items, view-major; a power of two): 256 frames of 1080p
+// need about 1,300 tiles per microsecond and one counter serves about 88
+// dequeues per microsecond, so the 32 heads at 16 tiles each run at a
+// thirtieth of their ceiling. A dequeue is a round trip the wave waits for,
+// a division of the item number and, at 1080p (2,025 chunks of 16 per view),
+// mostly a refill of the wave's view records too; with the tail below, config
+// 2 at 1080p per frame, chunks of 8 / 16 / 32: 256 views 24.6 / 24.3 / 24.4 us,
+// 128 views 25.1 / 24.9 / 25.2, 64 views 25.6 / 25.6 / 26.0
+// (profiles/r09c_ab_chunk_size.log; chunks of 4: +2.8 % at 256).
 #ifndef RT_CHUNK0
-#define RT_CHUNK0 8
+#define RT_CHUNK0 16
 #endif
 constexpr int kChunk0 = RT_CHUNK0;
-// The launch's last kTailTiles0 tiles per wave of the grid are dealt one tile
-// per dequeue: a wave tile takes about 6 us of a wave's time with 8 waves on
-// its SIMD, so whole chunks alone left a tail of up to 50 us (measured: 35 us
-// more per launch than the tiled launch's), which the waves that finish
-// their last chunk early now fill tile by tile.
-#ifndef RT_TAIL_TILES0
-#define RT_TAIL_TILES0 4
-#endif
-constexpr int kTailTiles0 = RT_TAIL_TILES0;
+static_assert(kChunk0 >= 2 && kChunk0 <= 32 && (kChunk0 & (kChunk0 - 1)) == 0, "bulk chunk: a power of two, 2..32");
+// The persistent launch's schedule: chunk id c -> items [t, t_end) of `total`
+// on a grid of `waves` waves (the one function the kernel and the host-only
+// rt_debug_persistent_chunk call). Chunk sizes fall towards the end of the
+// launch: the bulk in chunks of kChunk0, then a region of chunks of
+// kChunk0 / 2, ... , of 2 and last of single tiles. The region of size s ends
+// where s * waves items are left, so it holds about a chunk per wave (the
+// singles two per wave), and a wave that takes the last chunk of size s has
+// s items per wave of smaller chunks behind it for the others: no wave runs
+// more than about a tile past the rest (a wave tile takes 4 to 22 us of a
+// wave's time with 8 waves on its SIMD, 10 us on average: the SIMD issues
+// oldest wave first, so its youngest waves are its slowest all launch long).
+// That holds only because a wave takes its next chunk when it needs it
+// (render_persistent0). A launch smaller than its tail has the later regions
+// only. Ids past the last chunk
+// give an empty range. total < 2^30 (persistent_groups), so nothing here
+// leaves int: the region sizes come from total / s, never from s * waves.
+struct ChunkRange {
+    int t, t_end;
+};
+__host__ __device__ inline ChunkRange persistent_chunk(int c, int total, int waves) {
+    int start = 0;
+#pragma unroll
+    for (int s = kChunk0; s >= 2; s >>= 1) {
+        const int left = (total - start) / s - waves;  // chunks of s before s * waves items are left
+        const int n = left > 0 ? left : 0;
+        if (c < n) return {start + c * s, start + c * s + s};
+        c -= n;
+        start += n * s;
+    }
+    return c < total - start ? ChunkRange{start + c, start + c + 1} : ChunkRange{total, total};
+}
 // Automatic persistence (RT_OPT_PERSISTENT0 1) from this many wave tiles per
 // resident wave. Measured on config 2 at 1080p, tiled -> persistent per
-// launch: 9 views (36 tiles per wave) 271 -> 304 us, 16: 455 -> 474, 32:
-// 879 -> 885, 48 (190 per wave): 1300 -> 1287, 64: 1720 -> 1686, 128:
-// 3390 -> 3280, 256: 6.66 -> 6.37 ms. The persistent launch costs about 43 us
-// more per launch and 4.6 % less per view, so it pays from about 40 views.
+// launch: 9 views (36 tiles per wave) 270 -> 300 us, 16: 454 -> 467, 24:
+// 665 -> 668, 32: 877 -> 864, 48 (190 per wave): 1296 -> 1257, 64: 1714 ->
+// 1645, 128: 3379 -> 3190, 256: 6.67 -> 6.26 ms
+// (profiles/r09f_persistent_threshold.log). Through 9 and 256 views the
+// tiled launch costs 36 us + 25.9 us per view, the persistent one 83 us +
+// 24.1 us per view: it pays from about 26 views now (from 40 with the first
+// schedule); the threshold has not been moved yet.
 constexpr int kPersistentMinTilesPerWave = 192;
 // Work-groups of the persistent grid for a plain depth-0 launch on a kernel
 // with `resident` resident work-groups on the device, 0: the tiled launch.
@@ -340,6 +372,31 @@ constexpr int kQueues = 32;                            // wave-tile queues of a 
 constexpr int kQueueStride = 64;                       // ints: each counter on a 256-B line of its own
 constexpr int kSchedInts = 2 * kQueues * kQueueStride; // heads + done counters of one launch
 constexpr int kSchedSlots = 64;                        // launches that may be in flight at once
+// The persistent launch's waves and queues. Work-groups go to the chip's
+// eight XCDs in turn, so with queue g % kQueues every queue was served by the
+// waves of one XCD (and one SIMD index) alone and an eighth of the launch's
+// chunks was tied to each XCD, whatever its speed: the queues ran dry up to
+// 190 us apart at 256 views of 1080p (profiles/r09a_persistent_trace.log).
+// Round r = g / kQueues of the grid's waves is therefore dealt to the queues
+// rotated by kQueueRotate0 * r (odd, so over kQueues rounds a wave slot of
+// the chip serves every queue): every round still maps onto the queues one to
+// one, so a grid of kQueues waves or more leaves no queue without a wave, and
+// the wave's first chunk is its round's chunk of its queue.
+#ifndef RT_QUEUE_ROTATE0
+#define RT_QUEUE_ROTATE0 5
+#endif
+constexpr int kQueueRotate0 = RT_QUEUE_ROTATE0;
+static_assert((kQueues & (kQueues - 1)) == 0, "the queue arithmetic masks with kQueues - 1");
+__host__ __device__ inline int persistent_queue(int g) { return (g + kQueueRotate0 * (g / kQueues)) & (kQueues - 1); }
+// Waves of queue q on a grid of `waves` waves: one per whole round, and one
+// more where the last, partial round reaches the queue.
+__host__ __device__ inline int persistent_queue_waves(int q, int waves) {
+    const int rounds = waves / kQueues, rest = waves & (kQueues - 1);
+    return rounds + (((q - kQueueRotate0 * rounds) & (kQueues - 1)) < rest ? 1 : 0);
+}
+// The chunk wave g starts with: the g / kQueues-th of its queue. The queue's
+// head then hands out the chunks from persistent_queue_waves on.
+__host__ __device__ inline int persistent_first_chunk(int g) { return (g & ~(kQueues - 1)) + persistent_queue(g); }
 
 struct DeviceScene {
     void *blob = nullptr;

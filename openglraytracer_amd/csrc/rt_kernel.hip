@@ -1251,12 +1251,50 @@ __device__ unsigned long long rt_phase_buf[kPhaseWaves * 16];
     do {                                         \
         if ((v) != -12345) RT_PHASE(k);      \
     } while (0)
+// The persistent grid's stamps (tools/persistent_trace.py; the buffer is
+// cleared before the launch): the clock the first time the wave passes, a
+// counter, and a span [t0_, now) counted in slot k, summed in k + 1 and its
+// longest kept in slot k2.
+#define RT_PHASE_WAVE (blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6))
+#define RT_PHASE_LANE0 ((threadIdx.x & 63) == 0 && RT_PHASE_WAVE < kPhaseWaves)
+#define RT_PHASE_SLOT(k) rt_phase_buf[RT_PHASE_WAVE * 16 + (k)]
+#define RT_PHASE_ONCE(k)                                                                 \
+    do {                                                                                 \
+        const unsigned long long now_ = __builtin_amdgcn_s_memrealtime();                \
+        if (RT_PHASE_LANE0 && RT_PHASE_SLOT(k) == 0) RT_PHASE_SLOT(k) = now_;   \
+    } while (0)
+#define RT_PHASE_COUNT(k, v)                                   \
+    do {                                                       \
+        if (RT_PHASE_LANE0) RT_PHASE_SLOT(k) += (v);  \
+    } while (0)
+#define RT_PHASE_CLOCK(name) const unsigned long long name = __builtin_amdgcn_s_memrealtime()
+#define RT_PHASE_SPAN(k, k2, t0_)                                                     \
+    do {                                                                              \
+        const unsigned long long d_ = __builtin_amdgcn_s_memrealtime() - (t0_);      \
+        if (RT_PHASE_LANE0) {                                                \
+            RT_PHASE_SLOT(k) += 1;                                                    \
+            RT_PHASE_SLOT((k) + 1) += d_;                                             \
+            if (d_ > RT_PHASE_SLOT(k2)) RT_PHASE_SLOT(k2) = d_;                       \
+        }                                                                             \
+    } while (0)
 #else
 #define RT_PHASE_AFTER(k, v) \
     do {                     \
     } while (0)
 #define RT_PHASE(k) \
     do {            \
+    } while (0)
+#define RT_PHASE_ONCE(k) \
+    do {                 \
+    } while (0)
+#define RT_PHASE_COUNT(k, v) \
+    do {                     \
+    } while (0)
+#define RT_PHASE_CLOCK(name) \
+    do {                     \
+    } while (0)
+#define RT_PHASE_SPAN(k, k2, t0_) \
+    do {                          \
     } while (0)
 #endif
 
@@ -1953,10 +1991,15 @@ constexpr bool kQueuedDepth(int depth) { return depth >= 2; }
 //    scene once (one barrier); after it no wave waits for another. The items
 //    are the launch's wave tiles, view-major (item t = tile t % T of view
 //    t / T, a view's tiles row by row), dealt in chunks of kChunk0
-//    consecutive items, the last kTailTiles0 per wave one by one (chunks
-//    of one): chunk c belongs to queue c % kQueues, wave g starts
-//    with chunk g and then takes its queue's next chunk from the atomic head,
-//    fetched one chunk ahead. Division by the frame's tile counts happens
+//    consecutive items whose size halves region by region towards the
+//    launch's end, down to single tiles (persistent_chunk). Chunk c belongs
+//    to queue c % kQueues; wave g serves queue persistent_queue(g) (rotated
+//    round by round, so every queue's waves are spread over the XCDs: with
+//    g % kQueues each XCD had an eighth of the launch to itself), starts with
+//    its round's chunk of that queue and then takes the queue's next chunk
+//    from the atomic head, when it has finished the one it holds: fetched a
+//    chunk ahead, every wave was committed to two chunks and the launch ended
+//    on the slowest such pair. Division by the frame's tile counts happens
 //    once per chunk; inside it the tile steps to its right-hand neighbour. The
 //    view comes from p.views_dev by scalar loads, and its frame constants
 //    into a slot of the wave's own in LDS (after the scene: kThreads / 64
@@ -1964,8 +2007,8 @@ constexpr bool kQueuedDepth(int depth) { return depth >= 2; }
 //    view changes — LDS operations of one wave complete in order, so the
 //    refill needs only a compiler fence. The trip count is bounded by the
 //    launch's chunks; the last wave of a queue to run dry resets its counters.
-//    Registers: only the item, the chunk's end, the tile's coordinates, the
-//    slot's view and the fetched head stay live across a tile. Every tile
+//    Registers: only the item, the chunk's end, the tile's coordinates and the
+//    slot's view stay live across a tile. Every tile
 //    reads the launch's arguments again, as a tiled work-group does (through
 //    a pointer the compiler cannot see through, so nothing derived from them
 //    is hoisted out of the loop and held in registers across the body: hoisted,
@@ -1984,6 +2027,7 @@ __device__ __forceinline__ float4 *persistent_slot(const LaunchParams &p, float4
 // the previous tile's reads and the next tile's: one wave, in-order LDS.
 __device__ __forceinline__ void persistent_refill(const LaunchParams &p, float4 *lds, int z) {
     float4 *const slot = persistent_slot(p, lds);
+    RT_PHASE_CLOCK(refill_t0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     int lane = threadIdx.x & 63;
@@ -1991,6 +2035,7 @@ __device__ __forceinline__ void persistent_refill(const LaunchParams &p, float4 
     for (int i = lane; i < p.n_frame_consts; i += 64) slot[i] = p.consts_dev[z * p.n_frame_consts + i];
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    RT_PHASE_SPAN(10, 12, refill_t0);  // (the stores have issued, so the records' load has returned)
 }
 // One item: wave tile (wx, wy) of view z, the view's records in the slot.
 template <int kShape, int kLaunch>
@@ -2038,6 +2083,13 @@ template <int kShape, int kLaunch>
 __device__ __forceinline__ void render_persistent0(float4 *lds) {
     static_assert((kLaunch & kLaunchPlain) != 0 && (kShape & kShapeMaskBytes) != 0, "plain shaped launches");
     __builtin_amdgcn_s_setprio(1);
+    RT_PHASE(0);
+#ifdef RT_PHASE_TRACE
+    if (RT_PHASE_LANE0) {  // where the wave runs: HW_ID (cu / simd / se), XCC_ID above it
+        // (slots 2-6 are the tile's own stamps, render_wave_tile)
+        RT_PHASE_SLOT(8) = __builtin_amdgcn_s_getreg((31 << 11) | 4) | (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32;
+    }
+#endif
     {
         const LaunchParams &p = launch_args();
         const float4 *blob = static_cast<const float4 *>(p.scene);
@@ -2045,45 +2097,43 @@ __device__ __forceinline__ void render_persistent0(float4 *lds) {
     }
     __syncthreads();
     __builtin_amdgcn_s_setprio(0);
-    // global wave g of queue q = g % kQueues, one of the queue's q_waves waves
+    RT_PHASE(13);
+    // global wave g of queue q = persistent_queue(g), one of the queue's q_waves waves
     const auto global_wave = [] {
         return static_cast<int>(blockIdx.x) * (kThreads / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     };
     const auto queue_waves = [](int q) {
-        return (static_cast<int>(gridDim.x) * (kThreads / 64) - q + kQueues - 1) / kQueues;
+        return persistent_queue_waves(q, static_cast<int>(gridDim.x) * (kThreads / 64));
     };
     int held = -1;  // the view whose records the slot holds
-    int c = global_wave();
+    int c = persistent_first_chunk(global_wave());
     for (;;) {
         int t, t_end, z, wx, wy;
         {
             const LaunchParams &p = launch_args();
             const int wtx = (p.width + 7) / 8, view_tiles = wtx * ((p.height + 7) / 8);
             const int total = view_tiles * p.n_views;  // (< 2^30: persistent_groups)
-            // the launch's last kTailTiles0 tiles per wave go out one at a
-            // time (the tail: else a chunk of a wave's time, 8 x 6 us)
-            const int tail_max = kTailTiles0 * static_cast<int>(gridDim.x) * (kThreads / 64);
-            const int body = (total - (total < tail_max ? total : tail_max)) / kChunk0;  // whole chunks
-            if (c >= body + (total - body * kChunk0)) break;
-            // the queue's next chunk, fetched a chunk ahead: the fetch waits
-            // together with the refill's load, then lives in a scalar register
-            const int q = global_wave() % kQueues;
-            int nxt = 0;
-            if ((threadIdx.x & 63) == 0) nxt = atomicAdd(p.sched + q * kQueueStride, 1);
-            t = c < body ? c * kChunk0 : body * kChunk0 + (c - body);
-            t_end = c < body ? t + kChunk0 : t + 1;
+            // the chunk's items: sizes fall towards the launch's end
+            // (rt_internal.h persistent_chunk), empty past the last chunk
+            const ChunkRange r_c = persistent_chunk(c, total, static_cast<int>(gridDim.x) * (kThreads / 64));
+            if (r_c.t >= r_c.t_end) break;
+            t = r_c.t;
+            t_end = r_c.t_end;
             z = t / view_tiles;
             const int r = t - z * view_tiles;
             wy = r / wtx;
             wx = r - wy * wtx;
+            RT_PHASE_ONCE(1);  // the wave's first chunk
+            if (t_end - t == 1) RT_PHASE_ONCE(14);  // its first single tile
+            RT_PHASE_COUNT(15, 1);  // chunks
             if (z != held) persistent_refill(p, lds, z);
             held = z;
-            c = (queue_waves(q) + __builtin_amdgcn_readfirstlane(nxt)) * kQueues + q;
         }
         for (; t < t_end; ++t) {
             const LaunchParams &p = launch_args();
             if (z != held) persistent_refill(p, lds, z);
             held = z;
+            RT_PHASE_COUNT(9, 1);  // tiles
             persistent_tile<kShape, kLaunch>(p, lds, z, wx, wy);
             if (++wx == (p.width + 7) / 8) {
                 wx = 0;
@@ -2093,9 +2143,24 @@ __device__ __forceinline__ void render_persistent0(float4 *lds) {
                 }
             }
         }
+        {
+            // the queue's next chunk, taken only now that the wave needs it: a
+            // chunk reserved while the previous one was still to run (fetched
+            // a chunk ahead, as the launch first did) commits the wave to two
+            // chunks, up to 16 tiles while the rest of the chip drains — the
+            // 40 us every wave but a few idled at the end of a launch of any
+            // length (profiles/r09a_persistent_trace.log). The fetch's round
+            // trip was paid at the chunk's head before, too.
+            const LaunchParams &p = launch_args();
+            const int q = persistent_queue(global_wave());
+            int nxt = 0;
+            if ((threadIdx.x & 63) == 0) nxt = atomicAdd(p.sched + q * kQueueStride, 1);
+            c = (queue_waves(q) + __builtin_amdgcn_readfirstlane(nxt)) * kQueues + q;
+        }
     }
+    RT_PHASE(7);
     const LaunchParams &p = launch_args();
-    const int q = global_wave() % kQueues;
+    const int q = persistent_queue(global_wave());
     if ((threadIdx.x & 63) == 0 && atomicAdd(p.sched + (kQueues + q) * kQueueStride, 1) == queue_waves(q) - 1) {
         atomicExch(p.sched + q * kQueueStride, 0);  // every wave of the queue has made its last fetch
         atomicExch(p.sched + (kQueues + q) * kQueueStride, 0);
@@ -2462,8 +2527,8 @@ int scene_shape(const LaunchParams &p, int max_depth) {
 }
 
 int persistent_groups(const LaunchParams &p, int resident) {
-#if defined(RT_STATS) || defined(RT_CYCLES) || defined(RT_PHASE_TRACE)
-    return 0;  // (the instrumented builds' probes live in the tiled prologue)
+#if defined(RT_STATS) || defined(RT_CYCLES)
+    return 0;  // (these instrumented builds' probes live in the tiled prologue)
 #endif
     // a plain batch of one scene in its scene's shape, views and records in
     // device memory, counters to queue on

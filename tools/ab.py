@@ -11,8 +11,8 @@ Every build gets its own context and scene; each round times every build once
 — REPS/2 untimed launches, then one event pair around REPS back-to-back
 launches on a non-default stream, about 60 ms of GPU work, so the clock is the
 sustained one the bench sees rather than a short burst's — rounds interleaved
-so clock drift hits all builds alike. Prints the median and min per-frame
-(per-sample) kernel time and a hash of the frame.
+so clock drift hits all builds alike (AB_ROUNDS rounds, default 7). Prints the
+median and min per-frame (per-sample) kernel time and a hash of the frame.
 """
 import ctypes as C
 import hashlib
@@ -29,7 +29,7 @@ from oracle import scenes
 
 cfgs = sys.argv[1].split(",")
 builds = sys.argv[2:]
-ROUNDS = 7
+ROUNDS = int(os.environ.get("AB_ROUNDS", "7"))  # interleaved rounds per config
 
 
 def load(spec):

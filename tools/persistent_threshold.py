@@ -19,7 +19,7 @@ stream = torch.cuda.Stream()
 torch.cuda.set_stream(stream)
 for n_views, w, h in [(9, 320, 184), (9, 640, 368), (9, 960, 544), (16, 960, 544), (32, 960, 544),
                       (9, 1920, 1080), (12, 1920, 1080), (16, 1920, 1080), (24, 1920, 1080), (32, 1920, 1080),
-                      (48, 1920, 1080), (64, 1920, 1080), (128, 1920, 1080)]:
+                      (48, 1920, 1080), (64, 1920, 1080), (128, 1920, 1080), (256, 1920, 1080)]:
     views = [rt.make_view(None, k / 60.0) for k in range(n_views)]
     out = torch.empty((n_views, h, w, 4), dtype=torch.float32, device="cuda")
     tiles = n_views * ((w + 7) // 8) * ((h + 7) // 8)
