@@ -137,6 +137,42 @@ int rt_bench_objects(int n_spheres, uint64_t seed, rt_object *out);
 /* cam == NULL: the reference orbit camera at `time`. */
 int rt_make_view(const rt_camera *cam, float time, rt_view *out);
 
+/* ---- scenes as functions of `time` (host functions, no GPU) ------------
+ * The reference moves its objects inside the shader from the one uniform
+ * `time` (raytrace_compute.glsl:236-237, :261-321). Here that motion is
+ * described per object by scalar channels; a zero-initialised rt_object_anim
+ * means "static", so an existing scene describes itself. Every expression is
+ * float32, in exactly the written operation order, with no fused
+ * multiply-add; sin is the reference GL's run-time sin (gallivm's polynomial,
+ * rt_glmath.h). The forms are kept apart on purpose: 0 + x and x differ for
+ * x = -0. `k` is the folded constant the reference's GL forms (time_scale * K
+ * = 0.4f * K, :236).
+ * Range of `time`: the run-time sin / cos truncate |angle in radians| * 4/pi
+ * to an int, so every sin argument time * k, and every angle (degrees times
+ * pi / 180), must stay below 2^31 * pi / 4 in magnitude; beyond that host and
+ * device differ. */
+#define RT_ANIM_NONE        0  /* the base object's value, unchanged            */
+#define RT_ANIM_RATE        1  /* time * k                                      */
+#define RT_ANIM_RATE_OFFSET 2  /* c + time * k                                  */
+#define RT_ANIM_SIN         3  /* sin(time * k) * a                             */
+#define RT_ANIM_SIN_OFFSET  4  /* a * sin(time * k) + c                         */
+typedef struct rt_anim_channel { int32_t kind; float a, k, c; } rt_anim_channel;
+typedef struct rt_object_anim {
+    rt_anim_channel scale;        /* multiplies box_mins and box_maxs componentwise */
+    rt_anim_channel position[3];  /* replaces position[i]                           */
+    rt_anim_channel angles[3];    /* replaces angles[i] (degrees)                   */
+} rt_object_anim;
+/* The shipped scene's rules (:261-321) in this form: base[] are its objects
+ * with the animated fields at their time-0 values, anim[] their channels. */
+int rt_reference_animation(rt_object base[RT_REFERENCE_OBJECTS], rt_object_anim anim[RT_REFERENCE_OBJECTS]);
+/* out[i] = base[i] with its channels evaluated at `time` (out may be base).
+ * For rt_reference_animation the result equals rt_reference_objects(time)
+ * byte for byte. An object's kind (box, sphere or null) is the one its BASE
+ * has: the animated entry points below lay the scene out once, from the base
+ * objects, so a scale channel that passes through 0 does not turn a box into
+ * a sphere there (rt_scene_create of this function's output would). */
+int rt_animate_objects(const rt_object *base, const rt_object_anim *anim, int n_objs, float time, rt_object *out);
+
 /* The transforms a box object is intersected with, as the reference's GL
  * evaluates them per ray (raytrace_compute.glsl:650-652, :718, replacing
  * calc_transform_matrix / inverse / transpose(inverse(mat3(.)))):
@@ -257,6 +293,49 @@ int rt_render_batch(rt_context *ctx, const rt_scene *scene, const rt_view *views
 int rt_render_batch_scenes(rt_context *ctx, const rt_scene *const *scenes, const rt_view *views, int n_views,
                            int width, int height, int max_depth, int block_rows, int n_shards, int shard,
                            float *out_device, void *hip_stream);
+
+/* ---- device-side animation ---------------------------------------------
+ * An animated scene: the base objects and their channels, resident on the
+ * device. A render at `time` runs an animate kernel on the call's stream
+ * that evaluates the channels and rewrites the time-dependent parts of the
+ * scene (the boxes' transforms and their culling data), then the existing
+ * render: no host rebuild, no upload and no host synchronisation per frame
+ * (the reference: one uniform, raytrace_compute.glsl:236-237, main.cpp:226).
+ * The frame is bit-identical to rt_scene_update(rt_animate_objects(time))
+ * followed by the corresponding existing render call.
+ *
+ * Channels are supported on box objects only: an animated sphere (or null
+ * object) is refused with RT_ERR_UNSUPPORTED (moving spheres would need the
+ * sphere BVH, the cones and the candidate lists rebuilt on the device).
+ * Spheres may be present and static. A scene with a RATE / RATE_OFFSET
+ * channel on a position or on the scale is laid out for |time| <= 1e4 (its
+ * culling margins grow with the farthest the boxes can get); a render outside
+ * that range returns RT_ERR_UNSUPPORTED. `time` must also respect the sin /
+ * cos range above. A scene of 33-256 spheres gets its origin-sphere lists at
+ * creation, in each of the max_frames frame slots.
+ *
+ * max_frames (1..RT_MAX_BATCH): the frames that may be in flight at once,
+ * each in a slot of its own; a call takes the next slot(s) and, when a slot
+ * was last read on another stream, waits for that on the device
+ * (hipStreamWaitEvent), never on the host. RT_ERR_INVALID for a NULL
+ * pointer, a channel kind outside RT_ANIM_*, max_frames out of range, or
+ * (rt_render_batch_animated) n_views > max_frames.
+ * rt_last_kernel_ms after these calls covers the render launch or launches
+ * only, not the animate launch. An rt_anim that outlives its context is
+ * still destroyed safely (synchronously), like a scene. */
+typedef struct rt_anim rt_anim;
+int rt_anim_create(rt_context *ctx, const rt_object *base, const rt_object_anim *anim, int n_objs,
+                   const rt_material *mats, int n_mats, const rt_light *lights, int n_lights, int max_frames,
+                   rt_anim **out);
+void rt_anim_destroy(rt_anim *anim);
+/* rt_render with the objects at `time` too: cam NULL = the orbit camera at `time`. */
+int rt_render_animated(rt_context *ctx, rt_anim *anim, const rt_camera *cam, float time, int width, int height,
+                       int max_depth, int row_begin, int row_end, float *out, int out_is_device, void *hip_stream);
+/* rt_render_batch_scenes without the scenes: frame k shows the objects at
+ * times[k] through views[k] (views NULL: the orbit camera at times[k]). */
+int rt_render_batch_animated(rt_context *ctx, rt_anim *anim, const rt_view *views, const float *times, int n_views,
+                             int width, int height, int max_depth, int block_rows, int n_shards, int shard,
+                             float *out_device, void *hip_stream);
 
 /* Monte-Carlo extension (the reference has one
  * ray per pixel): adds, for every pixel of rows [row_begin, row_end), the sum

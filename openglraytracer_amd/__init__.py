@@ -79,6 +79,11 @@ def lib():
             "rt_render_multi": ([vp, vp, vp, f, i, i, i, i, vp, i], i),
             "rt_render_multi_view": ([vp, vp, vp, i, i, i, i, vp, i], i),
             "rt_multi_last_ms": ([vp, vp, vp, vp], i),
+            "rt_reference_animation": ([vp, vp], i), "rt_animate_objects": ([vp, vp, i, f, vp], i),
+            "rt_anim_create": ([vp, vp, vp, i, vp, i, vp, i, i, vp], i), "rt_anim_destroy": ([vp], None),
+            "rt_render_animated": ([vp, vp, vp, f, i, i, i, i, i, vp, i, vp], i),
+            "rt_render_batch_animated": ([vp, vp, vp, vp, i, i, i, i, i, i, i, vp, vp], i),
+            "rt_debug_anim_blob": ([vp, f, vp, C.c_longlong], C.c_longlong),
         }
         for name, (args, res) in sig.items():
             fn = getattr(L, name)
@@ -116,6 +121,24 @@ def reference_camera(time=0.0):
     c = Camera()
     _check(lib().rt_reference_camera(time, C.byref(c)))
     return c
+
+
+def reference_animation():
+    """rt_reference_animation: the shipped scene as (base objects, channels)."""
+    base = (Object * 5)()
+    anim = (abi.ObjectAnim * 5)()
+    _check(lib().rt_reference_animation(base, anim))
+    return list(base), list(anim)
+
+
+def animate_objects(base, anim, time):
+    """rt_animate_objects: the objects at `time` (host, float32 as written)."""
+    n = len(base)
+    b = (Object * max(n, 1))(*base)
+    a = (abi.ObjectAnim * max(n, 1))(*anim)
+    out = (Object * max(n, 1))()
+    _check(lib().rt_animate_objects(b, a, n, time, out))
+    return list(out[:n])
 
 
 def bench_objects(n_spheres, seed=0):
@@ -303,6 +326,83 @@ class Scene:
     @property
     def handle(self):
         return self._h
+
+
+class Anim:
+    """Device-resident animated scene (rt_anim_create): base objects and their
+    channels; `max_frames` frames may be in flight at once. Defaults: the
+    reference's 7 materials and 3 lights."""
+
+    def __init__(self, ctx, base, anim, materials=None, lights=None, max_frames=1):
+        materials = materials if materials is not None else reference_materials()
+        lights = lights if lights is not None else reference_lights()
+        objs = (Object * max(len(base), 1))(*base)
+        an = (abi.ObjectAnim * max(len(anim), 1))(*anim)
+        mats = (Material * len(materials))(*materials)
+        lts = (Light * max(len(lights), 1))(*lights)
+        self._h = C.c_void_p()
+        _check(lib().rt_anim_create(ctx.handle, objs, an, len(base), mats, len(materials), lts, len(lights),
+                                    max_frames, C.byref(self._h)))
+        self.ctx = ctx
+        self.max_frames = max_frames
+
+    def close(self):
+        if self._h:
+            lib().rt_anim_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def debug_blob(self, time):
+        """The slot blob the animate kernel leaves at `time` (bytes; a
+        development hook, rt_debug_anim_blob)."""
+        n = lib().rt_debug_anim_blob(self._h, time, None, 0)
+        if n < 0:
+            raise RTError(int(n), lib().rt_last_error().decode())
+        buf = np.zeros(int(n), np.uint8)
+        n = lib().rt_debug_anim_blob(self._h, time, buf.ctypes.data, buf.size)
+        if n < 0:
+            raise RTError(int(n), lib().rt_last_error().decode())
+        return buf
+
+
+def render_animated(ctx, anim, width, height, max_depth=0, time=0.0, camera=None, rows=None):
+    """rt_render_animated to a host array, synchronously: the objects and (with
+    camera None) the orbit camera at `time`."""
+    r0, r1 = rows if rows is not None else (0, height)
+    out = surface(ctx.output, max(r1 - r0, 1), max(width, 1))
+    _check(lib().rt_render_animated(ctx.handle, anim.handle, C.byref(camera) if camera is not None else None, time,
+                                    width, height, max_depth, r0, r1, out.ctypes.data, 0, None))
+    return out[: r1 - r0, :width]
+
+
+def render_animated_device(ctx, anim, out_ptr, width, height, max_depth=0, time=0.0, camera=None, rows=None,
+                           stream=None):
+    """rt_render_animated into device memory; asynchronous on `stream`."""
+    r0, r1 = rows if rows is not None else (0, height)
+    _check(lib().rt_render_animated(ctx.handle, anim.handle, C.byref(camera) if camera is not None else None, time,
+                                    width, height, max_depth, r0, r1, C.c_void_p(out_ptr), 1,
+                                    C.c_void_p(stream) if stream else None))
+
+
+def render_batch_animated(ctx, anim, out_ptr, width, height, max_depth, times, views=None, block_rows=8, n_shards=1,
+                          shard=0, stream=None):
+    """K = len(times) animated frames (rt_render_batch_animated): frame k
+    shows the objects at times[k] through views[k] (None: the orbit camera at
+    times[k]), into device memory (K, rows, width, C)."""
+    t = (C.c_float * len(times))(*[float(x) for x in times])
+    arr = (View * len(views))(*views) if views is not None else None
+    _check(lib().rt_render_batch_animated(ctx.handle, anim.handle, arr, t, len(times), width, height, max_depth,
+                                          block_rows, n_shards, shard, C.c_void_p(out_ptr),
+                                          C.c_void_p(stream) if stream else None))
 
 
 def surface(fmt, *shape):

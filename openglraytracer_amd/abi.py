@@ -32,6 +32,11 @@ RT_OUTPUT_RGB32F = 2
 RT_MAX_BATCH = 256
 RT_MULTI_RCCL = 0
 RT_MULTI_COPY = 1
+RT_ANIM_NONE = 0
+RT_ANIM_RATE = 1
+RT_ANIM_RATE_OFFSET = 2
+RT_ANIM_SIN = 3
+RT_ANIM_SIN_OFFSET = 4
 
 # material indices of the reference table (raytrace_compute.glsl:74-157)
 MATERIAL1, MATERIAL2, RED_GLASS, GREEN_GLASS, BLUE_GLASS, MIRROR, WALL = range(7)
@@ -60,6 +65,16 @@ class Light(C.Structure):
 class Camera(C.Structure):
     _fields_ = [("position", F3), ("angles", F3), ("v_fov", C.c_float), ("aspect", C.c_float),
                 ("near_plane", C.c_float), ("far_plane", C.c_float)]
+
+
+class AnimChannel(C.Structure):
+    """rt_anim_channel: one scalar of an object as a function of time."""
+    _fields_ = [("kind", C.c_int32), ("a", C.c_float), ("k", C.c_float), ("c", C.c_float)]
+
+
+class ObjectAnim(C.Structure):
+    """rt_object_anim: zero-initialised = static."""
+    _fields_ = [("scale", AnimChannel), ("position", AnimChannel * 3), ("angles", AnimChannel * 3)]
 
 
 def array(struct, items):

@@ -1,0 +1,257 @@
+// rt_anim.hip — the animate kernel: a scene's time-dependent parts rebuilt on
+// the GPU, in stream order ahead of the render that reads them (include/rt.h,
+// rt_anim; the reference moves its objects inside the shader from the uniform
+// `time`, raytrace_compute.glsl:236-237, :261-321).
+//
+// One 256-thread work-group per frame rewrites, in that frame's slot blob,
+// what build_scene (rt_scene.cpp) derives from the boxes' animated fields and
+// nothing else:
+//   1. records: one lane per box evaluates the channels (rt_anim.h) and the
+//      reference GL's transform chain (rt_glmath.h, the text the host runs:
+//      bit-identical) and stores the BoxRec's matrices, scaled extents,
+//      w2l_w0 and translate_only; a lane of another wave the box's
+//      light_inside and bounding sphere (float64);
+//   2. the (box, light) separating planes (scenes of several boxes) and, for
+//      the LDS direction masks' box bits, every (box, live light) cone;
+//   3. the direction masks: one thread per texel ORs the boxes' bits into the
+//      static spheres' template mask.
+// The culling data (light_inside, planes, mask bits) use build_scene's
+// inequalities and margins in float64; they need not equal the host's bit for
+// bit (the device's double sin / cos may differ in the last place) and are as
+// conservative: culling changes no pixel. Barriers only between the phases;
+// every store is a plain vector store.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "rt_anim.h"
+
+namespace rtamd {
+
+namespace {
+
+constexpr int kAnimThreads = 256;
+
+struct BoxCone {  // a box's bounding sphere seen from a live light (build_direction_masks)
+    double ax[3], ch, sh, every;
+};
+
+// LDS: [flag, 16 B][n float4 bounding spheres][n x n_live BoxCone], n = the
+// boxes with mask bits
+__host__ __device__ inline size_t lds_spheres_at() { return 16; }
+__host__ __device__ inline size_t lds_cones_at(int n_mask_boxes) { return 16 + static_cast<size_t>(n_mask_boxes) * 16; }
+
+// build_scene's float64 rotation of an object (culling only): Rz(yaw) Rx(pitch)
+// Ry(roll), each angle the float DEG_TO_RAD * deg; R[col][row].
+__device__ void rotation64(const float ang[3], double R[3][3]) {
+    auto rot = [](int axis, float deg, double r[3][3]) {
+        const double a = static_cast<double>(glf::kDegToRad * deg);
+        double c, s;
+        sincos(a, &s, &c);
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) r[i][j] = i == j ? 1.0 : 0.0;
+        if (axis == 0) { r[1][1] = c; r[1][2] = s; r[2][1] = -s; r[2][2] = c; }
+        if (axis == 1) { r[0][0] = c; r[0][2] = -s; r[2][0] = s; r[2][2] = c; }
+        if (axis == 2) { r[0][0] = c; r[0][1] = s; r[1][0] = -s; r[1][1] = c; }
+    };
+    auto mul = [](const double a[3][3], const double b[3][3], double r[3][3]) {
+        for (int c = 0; c < 3; ++c)
+            for (int w = 0; w < 3; ++w) r[c][w] = a[0][w] * b[c][0] + a[1][w] * b[c][1] + a[2][w] * b[c][2];
+    };
+    double z[3][3], x[3][3], y[3][3], zx[3][3];
+    rot(2, ang[1], z);
+    rot(0, ang[0], x);
+    rot(1, ang[2], y);
+    mul(z, x, zx);
+    mul(zx, y, R);
+}
+
+__global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams p) {
+    extern __shared__ double lds_raw[];
+    unsigned char *lds = reinterpret_cast<unsigned char *>(lds_raw);
+    const AnimTable &T = *reinterpret_cast<const AnimTable *>(p.table);
+    const int frame = blockIdx.x, tid = threadIdx.x;
+    const float time = p.times[frame];
+    unsigned char *blob = p.blobs + static_cast<size_t>((p.first_slot + frame) % p.n_slots) * p.slot_bytes;
+    const int nb = T.n_boxes, nl = T.n_lights;
+    const int n_mask_boxes = T.dmask_box ? nb : 0;
+    int *bad = reinterpret_cast<int *>(lds);  // 1: an animated field the plane test looks at is not finite
+    float4 *bsph = reinterpret_cast<float4 *>(lds + lds_spheres_at());
+    BoxCone *cones = reinterpret_cast<BoxCone *>(lds + lds_cones_at(n_mask_boxes));
+    const rt_object *base = reinterpret_cast<const rt_object *>(p.table + T.off_base);
+    const rt_object_anim *anim = reinterpret_cast<const rt_object_anim *>(p.table + T.off_anim);
+    const float4 *light = reinterpret_cast<const float4 *>(p.table + T.off_light);
+    BoxRec *boxes = reinterpret_cast<BoxRec *>(blob + static_cast<size_t>(p.off_boxes) * 16);
+    if (tid == 0) *bad = 0;
+    __syncthreads();
+
+    // ---- 1. records ------------------------------------------------------
+    // The first half of the work-group runs the float32 chain, the second half
+    // the float64 culling terms of the same boxes (other waves: side by side).
+    // The halves store disjoint words of a BoxRec; obj_index, material and the
+    // padding stay as build_scene laid them out.
+    constexpr int kHalf = kAnimThreads / 2;
+    if (tid < kHalf) {
+        for (int b = tid; b < nb; b += kHalf) {
+            const rt_object o = animate_object(base[b], anim[b], time);
+            float L[16], W[16], N[9];
+            glf::box_transforms(o.position, o.angles, L, W, N);
+            BoxRec &rec = boxes[b];
+            float w2l[12];
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 4; ++c) {  // stored row-major
+                    w2l[r * 4 + c] = W[c * 4 + r];
+                    rec.w2l[r * 4 + c] = W[c * 4 + r];
+                    rec.l2w[r * 4 + c] = L[c * 4 + r];
+                }
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) rec.nrm[r * 3 + c] = N[c * 3 + r];
+            int translate_only = 1;
+            bool finite = true;
+            for (int r = 0; r < 3; ++r) {
+                rec.mins[r] = o.box_mins[r];
+                rec.maxs[r] = o.box_maxs[r];
+                rec.w2l_w0[r] = w2l[r * 4 + 3] * 0.0f;
+                for (int c = 0; c < 3; ++c)
+                    if (w2l[r * 4 + c] != (r == c ? 1.0f : 0.0f)) translate_only = 0;
+                finite = finite && isfinite(o.position[r]) && isfinite(o.box_mins[r]) && isfinite(o.box_maxs[r]);
+            }
+            rec.translate_only = translate_only;
+            if (!finite) *bad = 1;
+        }
+    } else {
+        for (int b = tid - kHalf; b < nb; b += kHalf) {
+            const rt_object o = animate_object(base[b], anim[b], time);
+            // lights strictly inside the box by build_scene's margin (float64)
+            double R[3][3];
+            rotation64(o.angles, R);
+            uint32_t inside = 0;
+            for (int j = 0; j < nl && j < 32; ++j) {
+                const float4 lj = light[j];
+                const double d[3] = {double(lj.x) - double(o.position[0]), double(lj.y) - double(o.position[1]),
+                                     double(lj.z) - double(o.position[2])};
+                bool in = true;
+                for (int r = 0; r < 3; ++r) {
+                    const double lp = R[r][0] * d[0] + R[r][1] * d[1] + R[r][2] * d[2];  // the inverse rotation
+                    const double m =
+                        0.05 + 1e-4 * (fabs(double(o.box_mins[r])) + fabs(double(o.box_maxs[r])) + fabs(lp));
+                    in = in && isfinite(lp) && double(o.box_mins[r]) + m < lp && lp < double(o.box_maxs[r]) - m;
+                }
+                if (in) inside |= 1u << j;
+            }
+            boxes[b].light_inside = inside;
+            if (b < n_mask_boxes) {
+                // the bounding sphere that carries the box's mask bit (build_scene)
+                double c[3], h2 = 0.0;
+                for (int r = 0; r < 3; ++r) {
+                    c[r] = 0.5 * (double(o.box_mins[r]) + double(o.box_maxs[r]));
+                    const double e = 0.5 * (double(o.box_maxs[r]) - double(o.box_mins[r]));
+                    h2 += e * e;
+                }
+                double w[3];
+                for (int r = 0; r < 3; ++r)
+                    w[r] = R[0][r] * c[0] + R[1][r] * c[1] + R[2][r] * c[2] + double(o.position[r]);
+                const double wl = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+                const double rad = sqrt(h2) * 1.001 + 1e-3 * (1.0 + wl);
+                bsph[b] = make_float4(static_cast<float>(w[0]), static_cast<float>(w[1]), static_cast<float>(w[2]),
+                                      isfinite(rad) ? static_cast<float>(rad * (1.0 + 1e-6)) : HUGE_VALF);
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- 2. planes and cones ---------------------------------------------
+    if (p.off_bplane >= 0) {
+        // per (box, light) the face plane with the light farthest beyond it,
+        // in the float32 transform just stored (build_scene, "Round 6")
+        float4 *bplane = reinterpret_cast<float4 *>(blob + static_cast<size_t>(p.off_bplane) * 16);
+        const bool finite = T.finite && !*bad;
+        for (int i = tid; i < nb * nl; i += kAnimThreads) {
+            const int b = i / nl, j = i % nl;
+            const BoxRec &B = boxes[b];
+            const float4 lj = light[j];
+            const double Lp[3] = {lj.x, lj.y, lj.z};
+            double best = -HUGE_VAL, bn[3] = {0, 0, 0}, bw = 0, bm = 0;
+            for (int a = 0; a < 3 && finite; ++a)
+                for (int sgn = -1; sgn <= 1; sgn += 2) {
+                    const double face = sgn > 0 ? B.maxs[a] : B.mins[a];
+                    const double r[4] = {B.w2l[4 * a], B.w2l[4 * a + 1], B.w2l[4 * a + 2], B.w2l[4 * a + 3]};
+                    const double sl = sgn * (r[0] * Lp[0] + r[1] * Lp[1] + r[2] * Lp[2] + r[3] - face);
+                    if (sl > best) {
+                        best = sl;
+                        for (int k = 0; k < 3; ++k) bn[k] = sgn * r[k];
+                        bw = sgn * (r[3] - face);
+                        bm = 1e-3 + 1e-5 * (T.extent + fabs(r[3]) + fabs(face));
+                    }
+                }
+            float4 out = make_float4(0.0f, 0.0f, 0.0f, -HUGE_VALF);
+            if (finite && isfinite(best) && isfinite(bw) && best > 0.01 + 2.0 * bm)
+                out = make_float4(static_cast<float>(bn[0]), static_cast<float>(bn[1]), static_cast<float>(bn[2]),
+                                  static_cast<float>(bw - bm));
+            bplane[i] = out;
+        }
+    }
+    for (int i = tid; i < n_mask_boxes * nl; i += kAnimThreads) {
+        const int b = i / nl, j = i % nl;
+        const float4 lj = light[j];
+        const int li = __float_as_int(lj.w);
+        if (li < 0) continue;  // a dead light has no mask
+        const float4 s = bsph[b];
+        const double v[3] = {double(s.x) - double(lj.x), double(s.y) - double(lj.y), double(s.z) - double(lj.z)};
+        const double d = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        const double rp = double(s.w) + 0.021 + 1e-3 * d;
+        BoxCone c = {{0.0, 0.0, 0.0}, 0.0, 0.0, 0.0};
+        if (!(isfinite(d) && isfinite(rp)) || d <= rp) {
+            c.every = 1.0;
+        } else {
+            for (int k = 0; k < 3; ++k) c.ax[k] = v[k] / d;
+            const double half = asin(fmin(1.0, rp / d));
+            c.ch = cos(half + 1e-3);
+            c.sh = sin(half + 1e-3);
+        }
+        cones[b * T.n_live + li] = c;
+    }
+    if (n_mask_boxes == 0) return;  // (uniform: every thread of the launch)
+    __syncthreads();
+
+    // ---- 3. direction masks: the texel test, texel by texel --------------
+    const int texels = 6 * T.dmask_n * T.dmask_n;
+    const double *cone_tab = reinterpret_cast<const double *>(p.table + T.off_cone);
+    const unsigned char *tmpl = p.table + T.off_mask;
+    unsigned char *dmask = blob + static_cast<size_t>(p.off_dmask) * 16;
+    for (int i = tid; i < T.n_live * texels; i += kAnimThreads) {
+        const int li = i / texels, t = i % texels;
+        const double *w = cone_tab + 5 * static_cast<size_t>(t);
+        const double ca = w[3], sa = w[4];
+        uint64_t bits = 0;
+        for (int b = 0; b < n_mask_boxes; ++b) {
+            const BoxCone &c = cones[b * T.n_live + li];
+            // cos(alpha + half + 1e-3), less 1e-12 for rounding (build_direction_masks)
+            const double lim = ca * c.ch - sa * c.sh - 1e-12;
+            const double dot = w[0] * c.ax[0] + w[1] * c.ax[1] + w[2] * c.ax[2];
+            if (c.every != 0.0 || dot >= lim) bits |= uint64_t{1} << (T.n_spheres + b);
+        }
+        if (T.dmask_bytes == 2)
+            reinterpret_cast<uint16_t *>(dmask)[i] =
+                static_cast<uint16_t>(reinterpret_cast<const uint16_t *>(tmpl)[i] | bits);
+        else if (T.dmask_bytes == 4)
+            reinterpret_cast<uint32_t *>(dmask)[i] =
+                static_cast<uint32_t>(reinterpret_cast<const uint32_t *>(tmpl)[i] | bits);
+        else
+            reinterpret_cast<uint64_t *>(dmask)[i] = reinterpret_cast<const uint64_t *>(tmpl)[i] | bits;
+    }
+}
+
+}  // namespace
+
+size_t animate_lds(const AnimTable &t) {
+    const int n = t.dmask_box ? t.n_boxes : 0;
+    return lds_cones_at(n) + static_cast<size_t>(n) * t.n_live * sizeof(BoxCone);
+}
+
+hipError_t launch_animate(const AnimParams &p, int n_frames, size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL(animate_kernel, dim3(n_frames), dim3(kAnimThreads), lds, stream, p);
+    return hipGetLastError();
+}
+
+}  // namespace rtamd

@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 
+#include "rt_anim.h"
 #include "rt_internal.h"
 
 using namespace rtamd;
@@ -223,6 +224,48 @@ int rt_reference_objects(float time, rt_object out[RT_REFERENCE_OBJECTS]) {
     float mn3[3] = {-1, -1, -2}, mx3[3] = {1, 1, 2};
     make_object(out[3], mn3, mx3, -1.0f, 3, 4, 1, 45.0f + st(45.0f), 0, 45.0f + st(180.0f), RT_MAT_BLUE_GLASS);
     make_object(out[4], zero, zero, 2.0f, -3, 4, 1, 0, 0, 0, RT_MAT_RED_GLASS);
+    return RT_OK;
+}
+
+// rt_reference_objects' rules as channels (include/rt.h): base = the objects
+// with the animated fields at their time-0 values.
+int rt_reference_animation(rt_object base[RT_REFERENCE_OBJECTS], rt_object_anim anim[RT_REFERENCE_OBJECTS]) {
+    if (!base || !anim) { set_error("rt_reference_animation: null argument"); return RT_ERR_INVALID; }
+    const int rc = rt_reference_objects(0.0f, base);
+    if (rc != RT_OK) return rc;
+    std::memset(anim, 0, sizeof(rt_object_anim) * RT_REFERENCE_OBJECTS);
+    auto ch = [](int kind, float a, float k, float c) { return rt_anim_channel{kind, a, 0.4f * k, c}; };
+    // object 1 (:277-287): the mirror cube, +-1 scaled by 0.5 sin(0.5 st) + 1.5
+    for (int i = 0; i < 3; ++i) {
+        base[1].box_mins[i] = -1.0f;
+        base[1].box_maxs[i] = 1.0f;
+    }
+    anim[1].scale = ch(RT_ANIM_SIN_OFFSET, 0.5f, 0.5f, 1.5f);
+    anim[1].position[2] = ch(RT_ANIM_SIN, 1.0f, 3.0f, 0.0f);
+    anim[1].angles[1] = ch(RT_ANIM_RATE, 0.0f, 90.0f, 0.0f);
+    // object 2 (:289-297): the glass slab pitching by 10 sin(5 st)
+    anim[2].angles[0] = ch(RT_ANIM_SIN, 10.0f, 5.0f, 0.0f);
+    // object 3 (:299-307): the blue box turning about two axes
+    anim[3].angles[0] = ch(RT_ANIM_RATE_OFFSET, 0.0f, 45.0f, 45.0f);
+    anim[3].angles[2] = ch(RT_ANIM_RATE_OFFSET, 0.0f, 180.0f, 45.0f);
+    return RT_OK;
+}
+
+int rt_animate_objects(const rt_object *base, const rt_object_anim *anim, int n_objs, float time, rt_object *out) {
+    if (n_objs < 0 || (n_objs > 0 && (!base || !anim || !out))) {
+        set_error("rt_animate_objects: null argument or negative count");
+        return RT_ERR_INVALID;
+    }
+    for (int i = 0; i < n_objs; ++i) {
+        const rt_anim_channel *c = &anim[i].scale;  // 7 channels, contiguous
+        for (int k = 0; k < 7; ++k)
+            if (c[k].kind < RT_ANIM_NONE || c[k].kind > RT_ANIM_SIN_OFFSET) {
+                set_error("rt_animate_objects: object " + std::to_string(i) + " has a channel of unknown kind " +
+                          std::to_string(c[k].kind));
+                return RT_ERR_INVALID;
+            }
+    }
+    for (int i = 0; i < n_objs; ++i) out[i] = animate_object(base[i], anim[i], time);
     return RT_OK;
 }
 
@@ -1021,8 +1064,33 @@ int build_origin_lists_for(const std::vector<float4> &host, const DeviceScene &d
     return RT_OK;
 }
 
+int object_kind_of(const rt_object &o) { return object_kind(o); }
+
+double objects_extent(const rt_object *objs, int n_objs) {
+    double extent = 0.0;
+    for (int i = 0; i < n_objs; ++i) {
+        const rt_object &o = objs[i];
+        double e = std::sqrt(static_cast<double>(o.position[0]) * o.position[0] +
+                             static_cast<double>(o.position[1]) * o.position[1] +
+                             static_cast<double>(o.position[2]) * o.position[2]);
+        double corner = std::fabs(static_cast<double>(o.radius));
+        for (int a = 0; a < 3; ++a)
+            corner = std::max(corner, std::max(std::fabs(static_cast<double>(o.box_mins[a])),
+                                               std::fabs(static_cast<double>(o.box_maxs[a]))));
+        e += corner * std::sqrt(3.0);
+        if (std::isfinite(e)) extent = std::max(extent, e);
+    }
+    return extent;
+}
+
+MaskConeTable mask_cone_table(int n) {
+    const MaskCones &mc = mask_cones(n);
+    return MaskConeTable{n, mc.w.data(), mc.ca.data(), mc.sa.data()};
+}
+
 int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int n_mats, const rt_light *lights,
-                int n_lights, std::vector<float4> &blob, DeviceScene &ds, bool with_origin_lists) {
+                int n_lights, std::vector<float4> &blob, DeviceScene &ds, bool with_origin_lists,
+                double extent_floor) {
     std::vector<SphereRec> sph;
     std::vector<SphereMeta> smeta;
     std::vector<BoxRec> boxes;
@@ -1080,19 +1148,10 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
             boxes.push_back(b);
         }
     }
-    double extent = 0.0;  // |coordinate| bound of the finite objects (BVH margins)
-    for (int i = 0; i < n_objs; ++i) {
-        const rt_object &o = objs[i];
-        double e = std::sqrt(static_cast<double>(o.position[0]) * o.position[0] +
-                             static_cast<double>(o.position[1]) * o.position[1] +
-                             static_cast<double>(o.position[2]) * o.position[2]);
-        double corner = std::fabs(static_cast<double>(o.radius));
-        for (int a = 0; a < 3; ++a)
-            corner = std::max(corner, std::max(std::fabs(static_cast<double>(o.box_mins[a])),
-                                               std::fabs(static_cast<double>(o.box_maxs[a]))));
-        e += corner * std::sqrt(3.0);
-        if (std::isfinite(e)) extent = std::max(extent, e);
-    }
+    // |coordinate| bound of the finite objects (BVH margins); an animated
+    // scene's template passes the bound over its supported times (any larger
+    // value only widens the margins)
+    const double extent = std::max(objects_extent(objs, n_objs), extent_floor);
     std::vector<BvhNode> bvh;
     std::vector<uint32_t> blink;
     build_bvh(sph, smeta, bvh, blink, extent);

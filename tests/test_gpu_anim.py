@@ -1,0 +1,395 @@
+"""Device-side scene animation (include/rt.h, rt_anim): the animate kernel's
+records against the host's, and rt_render_animated / rt_render_batch_animated
+against the golden frames, the oracle and the host-update path
+(rt_scene_update of rt_animate_objects(time) + the existing render call) —
+every comparison bitwise."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import openglraytracer_amd as rt
+from conftest import GOLDEN, dev_zeros, load_fixture, manifest, parity_stats
+from openglraytracer_amd import abi
+from openglraytracer_amd.abi import AnimChannel, Light, Material, Object, ObjectAnim
+from oracle import port, scenes
+
+pytestmark = pytest.mark.gpu
+MAN = manifest()
+
+BOXREC = np.dtype([("w2l", "<u4", 12), ("l2w", "<u4", 12), ("nrm", "<u4", 9), ("mins", "<u4", 3), ("maxs", "<u4", 3),
+                   ("obj_index", "<i4"), ("material", "<i4"), ("light_inside", "<u4"), ("translate_only", "<i4"),
+                   ("w2l_w0", "<u4", 3), ("pad", "<i4", 2)])
+assert BOXREC.itemsize == 192
+EXACT_FIELDS = ("w2l", "l2w", "nrm", "mins", "maxs", "translate_only", "w2l_w0", "obj_index", "material")
+
+
+def host_boxes(objs, mats, lights):
+    """The BoxRecs build_scene makes of `objs` (rt_debug_scene_blob, host)."""
+    f = rt.lib().rt_debug_scene_blob
+    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
+    f.restype = C.c_int
+    oa, ma, la = (Object * len(objs))(*objs), (Material * len(mats))(*mats), (Light * max(len(lights), 1))(*lights)
+    meta = (C.c_int32 * 24)()
+    n = f(oa, len(objs), ma, len(mats), la, len(lights), None, 0, meta)
+    assert n > 0, rt.lib().rt_last_error()
+    buf = np.zeros(n, np.uint8)
+    assert f(oa, len(objs), ma, len(mats), la, len(lights), buf.ctypes.data, n, meta) == n
+    off, nb = meta[3] * 16, meta[18]
+    return np.frombuffer(buf[off:off + nb * 192].tobytes(), BOXREC), off, n
+
+
+def device_boxes(anim, t, off, nbytes, nb):
+    blob = anim.debug_blob(t)
+    assert blob.size == nbytes
+    return np.frombuffer(blob[off:off + nb * 192].tobytes(), BOXREC)
+
+
+def assert_same_records(dev, host, what):
+    assert len(dev) == len(host)
+    for name in EXACT_FIELDS:
+        assert np.array_equal(dev[name], host[name]), (what, name, dev[name], host[name])
+
+
+@pytest.fixture(scope="module")
+def shipped(gpu_ctx):
+    base, anim = rt.reference_animation()
+    a = rt.Anim(gpu_ctx, base, anim, max_frames=33)
+    yield a
+    a.close()
+
+
+def test_device_transforms_equal_the_host_at_the_golden_times(shipped):
+    """The animate kernel's BoxRecs of the shipped scene at the 32 probed times
+    of the llvmpipe box-transform vectors: bit for bit the host's."""
+    base, anim = rt.reference_animation()
+    mats, lights = rt.reference_materials(), rt.reference_lights()
+    z = np.load(os.path.join(GOLDEN, "box_llvmpipe.npz"))
+    assert len(z["time"]) == 32
+    for t in z["time"]:
+        host, off, n = host_boxes(rt.animate_objects(base, anim, float(t)), mats, lights)
+        assert_same_records(device_boxes(shipped, float(t), off, n, len(host)), host, float(t))
+        # every light_inside decision has 0.05 of margin: the same on both sides here
+        assert np.array_equal(device_boxes(shipped, float(t), off, n, len(host))["light_inside"], host["light_inside"])
+
+
+def test_device_transforms_equal_the_host_on_random_boxes(gpu_ctx):
+    """64 seeded (position, angles) sets, angles in [-720, 720], every channel
+    kind among them: one scene of 64 boxes, one launch."""
+    rng = np.random.default_rng(77)
+    base, anim = [], []
+    for i in range(64):
+        ext = rng.uniform(0.2, 2.0, 3)
+        base.append(scenes.box(tuple(-ext), tuple(ext), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), int(rng.integers(7))))
+        an = ObjectAnim()
+        for k in range(3):
+            kind = int(rng.integers(1, 5))
+            if kind in (abi.RT_ANIM_RATE, abi.RT_ANIM_RATE_OFFSET):
+                c = rng.uniform(-360.0, 360.0) if kind == abi.RT_ANIM_RATE_OFFSET else 0.0
+                an.angles[k] = AnimChannel(kind, 0.0, rng.uniform(-360.0, 360.0), c)
+            else:
+                c = rng.uniform(-360.0, 360.0) if kind == abi.RT_ANIM_SIN_OFFSET else 0.0
+                an.angles[k] = AnimChannel(kind, rng.uniform(-360.0, 360.0), rng.uniform(-9.0, 9.0), c)
+            an.position[k] = AnimChannel(abi.RT_ANIM_SIN_OFFSET, rng.uniform(-3.0, 3.0), rng.uniform(-5.0, 5.0),
+                                         rng.uniform(-6.0, 6.0))
+        if i % 3 == 0:
+            an.scale = AnimChannel(abi.RT_ANIM_SIN_OFFSET, 0.4, rng.uniform(-3.0, 3.0), 1.1)
+        anim.append(an)
+    mats, lights = rt.reference_materials(), rt.reference_lights()
+    a = rt.Anim(gpu_ctx, base, anim)
+    try:
+        for t in (1.0, -0.6171875):
+            objs = rt.animate_objects(base, anim, t)
+            assert max(abs(x) for o in objs for x in o.angles) <= 720.0
+            host, off, n = host_boxes(objs, mats, lights)
+            assert len(host) == 64
+            assert_same_records(device_boxes(a, t, off, n, 64), host, t)
+    finally:
+        a.close()
+
+
+@pytest.mark.parametrize("name", ["shipped_t0_d0_129x73", "shipped_t3.7_d0_160x90", "shipped_t11.25_d1_160x90",
+                                  "shipped_t0_d2_160x90", "shipped_t0_d4_64x36"])
+def test_golden_frames(gpu_ctx, shipped, name):
+    """rt_render_animated(cam = NULL, time): the reference's own render."""
+    m = MAN[name]
+    rgb, _ = load_fixture(name)
+    x0, y0, w, h = m["crop"]
+    g = rt.render_animated(gpu_ctx, shipped, m["width"], m["height"], m["max_depth"], m["time"], rows=(y0, y0 + h))
+    g = g[:, x0:x0 + w]
+    assert (g[..., 3] == 0).all()
+    s = parity_stats(g, rgb)
+    assert s["exact"] == 1.0, s
+
+
+def _tensor(fmt, *shape):
+    if fmt == abi.RT_OUTPUT_RGBA8:
+        return dev_zeros(shape + (4,), dtype=torch.uint8, device="cuda")
+    return dev_zeros(shape + (3 if fmt == abi.RT_OUTPUT_RGB32F else 4,), dtype=torch.float32, device="cuda")
+
+
+@pytest.mark.parametrize("fmt", [abi.RT_OUTPUT_RGBA32F, abi.RT_OUTPUT_RGBA8, abi.RT_OUTPUT_RGB32F])
+def test_equals_the_host_update_path(gpu_ctx, shipped, fmt):
+    """Shipped scene, 160x90, 24 times, depths 0 and 1, in each surface
+    format; rows 10-50 only and a 3-shard batch: each equal to rt_scene_update
+    of rt_animate_objects(time) + the existing call."""
+    base, anim = rt.reference_animation()
+    w, h = 160, 90
+    times = [float(np.float32(x)) for x in np.linspace(0.0, 17.25, 24)]
+    sc = rt.Scene(gpu_ctx, base)
+    gpu_ctx.set_output(fmt)
+    try:
+        for i, t in enumerate(times):
+            sc.update(rt.animate_objects(base, anim, t))
+            view = rt.make_view(None, t)
+            for depth in (0, 1):
+                want = rt.render(gpu_ctx, sc, w, h, depth, view=view)
+                got = rt.render_animated(gpu_ctx, shipped, w, h, depth, t)
+                assert np.array_equal(got, want, equal_nan=True), (t, depth)
+                if i % 6 == 0:
+                    band = rt.render_animated(gpu_ctx, shipped, w, h, depth, t, rows=(10, 50))
+                    assert np.array_equal(band, want[10:50], equal_nan=True), (t, depth, "rows")
+        # a 3-shard batch of 5 frames against rt_render_shard of the updated scene
+        bt = times[3:8]
+        for depth in (0, 1):
+            for shard in range(3):
+                rows = rt.shard_rows(h, 8, 3, shard)
+                out = _tensor(fmt, len(bt), rows, w)
+                rt.render_batch_animated(gpu_ctx, shipped, out.data_ptr(), w, h, depth, bt, block_rows=8, n_shards=3,
+                                         shard=shard)
+                got = out.cpu().numpy()
+                for k, t in enumerate(bt):
+                    sc.update(rt.animate_objects(base, anim, t))
+                    one = _tensor(fmt, rows, w)
+                    rt.render_shard(gpu_ctx, sc, one.data_ptr(), w, h, depth, 8, 3, shard, view=rt.make_view(None, t))
+                    assert np.array_equal(got[k], one.cpu().numpy(), equal_nan=True), (t, depth, shard)
+    finally:
+        gpu_ctx.set_output(abi.RT_OUTPUT_RGBA32F)
+        sc.close()
+
+
+@pytest.mark.parametrize("n,depth", [(3, 0), (9, 0), (33, 0), (3, 1), (9, 1), (33, 1), (9, 2)])
+def test_batches_equal_single_frames(gpu_ctx, shipped, n, depth):
+    """3 frames (views in the kernel arguments), 9 (the device-view path; the
+    split launches at depth 2) and 33 (with the calls before it, more than one
+    round of the 33 slots): each frame equals its rt_render_animated frame."""
+    w, h = 64, 36
+    times = [0.37 * k - 1.0 for k in range(n)]
+    out = dev_zeros((n, h, w, 4), dtype=torch.float32, device="cuda")
+    rt.render_batch_animated(gpu_ctx, shipped, out.data_ptr(), w, h, depth, times)
+    got = out.cpu().numpy()
+    for k, t in enumerate(times):
+        one = rt.render_animated(gpu_ctx, shipped, w, h, depth, t)
+        assert np.array_equal(got[k], one, equal_nan=True), (n, depth, k)
+
+
+def test_batch_with_explicit_views(gpu_ctx, shipped):
+    """views[k] given: the objects at times[k] seen from another time's orbit."""
+    w, h = 64, 36
+    times, cams = [0.5, 1.5, 2.5], [4.0, 0.0, 9.0]
+    views = [rt.make_view(None, c) for c in cams]
+    out = dev_zeros((3, h, w, 4), dtype=torch.float32, device="cuda")
+    rt.render_batch_animated(gpu_ctx, shipped, out.data_ptr(), w, h, 1, times, views=views)
+    got = out.cpu().numpy()
+    base, anim = rt.reference_animation()
+    for k in range(3):
+        sc = rt.Scene(gpu_ctx, rt.animate_objects(base, anim, times[k]))
+        try:
+            assert np.array_equal(got[k], rt.render(gpu_ctx, sc, w, h, 1, view=views[k]))
+        finally:
+            sc.close()
+
+
+def test_more_views_than_frames_in_flight_is_refused(gpu_ctx):
+    base, anim = rt.reference_animation()
+    a = rt.Anim(gpu_ctx, base, anim, max_frames=4)
+    try:
+        out = dev_zeros((9, 36, 64, 4), dtype=torch.float32, device="cuda")
+        with pytest.raises(rt.RTError) as e:
+            rt.render_batch_animated(gpu_ctx, a, out.data_ptr(), 64, 36, 0, [0.1 * k for k in range(9)])
+        assert e.value.code == abi.RT_ERR_INVALID
+        rt.render_batch_animated(gpu_ctx, a, out.data_ptr(), 64, 36, 0, [0.1 * k for k in range(4)])
+    finally:
+        a.close()
+
+
+EDGE_TIMES = [0.0, 1.0, 2.5]
+
+
+def edge_scene(seed):
+    """2-6 animated boxes + 0-12 static spheres (seed 16: 2 boxes + 40 spheres,
+    the wide masks and origin lists), 1-3 lights. Box 0 turns about x from an
+    angle of exactly 0 at t = 0 (translate_only flips); box 1 crosses light 0,
+    its centre on the light at t = 1 (light_inside and its plane flip), and
+    breathes (a scale channel); the other boxes get random channels."""
+    rng = np.random.default_rng(9100 + seed)
+    mats = rt.reference_materials()
+    lights = []
+    for _ in range(int(rng.integers(1, 4))):
+        lt = Light()
+        lt.position[:] = rng.uniform(-6.0, 6.0, 3)
+        lt.ambient[:] = rng.uniform(0.0, 0.2, 4)
+        lt.diffuse[:] = rng.uniform(0.2, 1.0, 4)
+        lt.specular[:] = rng.uniform(0.2, 1.0, 4)
+        lights.append(lt)
+    wide = seed == 16
+    n_boxes = 2 if wide else int(rng.integers(2, 7))
+    n_sph = 40 if wide else int(rng.integers(0, 13))
+    base, anim = [], []
+    for b in range(n_boxes):
+        ext = rng.uniform(0.4, 1.2, 3)
+        an = ObjectAnim()
+        pos, ang = rng.uniform(-6.0, 6.0, 3), rng.uniform(0.0, 360.0, 3)
+        if b == 0:
+            ang = np.zeros(3)
+            an.angles[0] = AnimChannel(abi.RT_ANIM_RATE, 0.0, float(rng.uniform(5.0, 40.0)), 0.0)
+        elif b == 1:
+            L = np.array(lights[0].position[:], np.float32)
+            k = np.array([3.0, -2.0, 0.5], np.float32)
+            for i in range(3):
+                an.position[i] = AnimChannel(abi.RT_ANIM_RATE_OFFSET, 0.0, float(k[i]), float(L[i] - k[i]))
+            an.scale = AnimChannel(abi.RT_ANIM_SIN_OFFSET, 0.3, float(rng.uniform(0.5, 3.0)), 1.0)
+        else:
+            for i in range(3):
+                kind = int(rng.integers(0, 5))
+                an.position[i] = AnimChannel(kind, float(rng.uniform(-2.0, 2.0)), float(rng.uniform(-1.5, 1.5)),
+                                             float(rng.uniform(-5.0, 5.0)))
+                kind = int(rng.integers(0, 5))
+                an.angles[i] = AnimChannel(kind, float(rng.uniform(-90.0, 90.0)), float(rng.uniform(-3.0, 3.0)),
+                                           float(rng.uniform(-180.0, 180.0)))
+            if rng.random() < 0.5:
+                an.scale = AnimChannel(abi.RT_ANIM_SIN_OFFSET, 0.5, float(rng.uniform(-2.0, 2.0)), 1.2)
+        base.append(scenes.box(tuple(-ext), tuple(ext * rng.uniform(0.5, 1.0, 3)), tuple(pos), tuple(ang),
+                               int(rng.integers(len(mats)))))
+        anim.append(an)
+    for _ in range(n_sph):
+        base.append(scenes.sphere(tuple(rng.uniform(-7.0, 7.0, 3)), float(rng.uniform(0.2, 1.0)),
+                                  int(rng.integers(len(mats)))))
+        anim.append(ObjectAnim())
+    order = rng.permutation(len(base))  # boxes and spheres interleaved in the object order
+    return [base[i] for i in order], [anim[i] for i in order], mats, lights, [int(np.where(order == b)[0][0])
+                                                                              for b in (0, 1)]
+
+
+@pytest.mark.parametrize("seed", range(17))
+def test_edges_that_flip_host_decisions(gpu_ctx, seed):
+    """Seeded scenes at 64x36, depths 0 and 2 (seed 16: depth 2): bit-exact
+    against the oracle with culling on and off, and against the host-update
+    path, at times where translate_only, light_inside and the separating
+    planes take both values."""
+    base, anim, mats, lights, (i0, i1) = edge_scene(seed)
+    w, h = 64, 36
+    a = rt.Anim(gpu_ctx, base, anim, materials=mats, lights=lights)
+    sc = None
+    flips = {"translate_only": set(), "light_inside": set()}
+    try:
+        for t in EDGE_TIMES:
+            objs = rt.animate_objects(base, anim, t)
+            host, _, _ = host_boxes(objs, mats, lights)
+            flips["translate_only"].add(int(host[list(host["obj_index"]).index(i0)]["translate_only"]))
+            flips["light_inside"].add(int(host[list(host["obj_index"]).index(i1)]["light_inside"]) & 1)
+            if sc is None:
+                sc = rt.Scene(gpu_ctx, objs, materials=mats, lights=lights)
+            else:
+                sc.update(objs, materials=mats, lights=lights)
+            for depth in ((2,) if seed == 16 else (0, 2)):
+                o = port.render(objs, w, h, depth, t, materials=mats, lights=lights)
+                got = rt.render_animated(gpu_ctx, a, w, h, depth, t)
+                upd = rt.render(gpu_ctx, sc, w, h, depth, view=rt.make_view(None, t))
+                gpu_ctx.set_culling(False)
+                try:
+                    off = rt.render_animated(gpu_ctx, a, w, h, depth, t)
+                finally:
+                    gpu_ctx.set_culling(True)
+                desc = (seed, t, depth, len(base), len(lights))
+                assert np.array_equal(got, o, equal_nan=True), (desc, "oracle", parity_stats(got, o))
+                assert np.array_equal(off, o, equal_nan=True), (desc, "culling off", parity_stats(off, o))
+                assert np.array_equal(got, upd, equal_nan=True), (desc, "host update", parity_stats(got, upd))
+    finally:
+        a.close()
+        if sc is not None:
+            sc.close()
+    assert flips["translate_only"] == {0, 1}, flips
+    assert flips["light_inside"] == {0, 1}, flips
+
+
+def test_static_scene_through_the_animated_path(gpu_ctx):
+    """Config 2's scene (the room box, 16 spheres, no channels) equals rt_render."""
+    objs = scenes.bench_objects(16)
+    a = rt.Anim(gpu_ctx, objs, [ObjectAnim() for _ in objs])
+    sc = rt.Scene(gpu_ctx, objs)
+    try:
+        for depth, t in ((0, 0.0), (0, 2.0), (2, 1.0)):
+            want = rt.render(gpu_ctx, sc, 160, 90, depth, view=rt.make_view(None, t))
+            assert np.array_equal(rt.render_animated(gpu_ctx, a, 160, 90, depth, t), want), (depth, t)
+    finally:
+        a.close()
+        sc.close()
+
+
+@pytest.mark.parametrize("two_streams", [False, True])
+def test_stream_order(gpu_ctx, two_streams):
+    """Two asynchronous frames at different times with no synchronisation
+    between them, into two buffers: on one caller stream (two slots), and on
+    two streams with max_frames = 1 (the second call's animate launch waits,
+    on the device, for the first call's render of the one slot)."""
+    base, anim = rt.reference_animation()
+    w, h, depth = 320, 180, 1
+    a = rt.Anim(gpu_ctx, base, anim, max_frames=1 if two_streams else 2)
+    try:
+        want = [rt.render_animated(gpu_ctx, a, w, h, depth, t) for t in (0.75, 6.5)]
+        s = [torch.cuda.Stream(), torch.cuda.Stream() if two_streams else None]
+        s[1] = s[1] or s[0]
+        outs = [dev_zeros((h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+        for k, t in enumerate((0.75, 6.5)):
+            rt.render_animated_device(gpu_ctx, a, outs[k].data_ptr(), w, h, depth, t, stream=s[k].cuda_stream)
+        for x in s:
+            x.synchronize()
+        for k in range(2):
+            assert np.array_equal(outs[k].cpu().numpy(), want[k]), k
+    finally:
+        a.close()
+
+
+def test_error_returns(gpu_ctx):
+    lib = rt.lib()
+    base, anim = rt.reference_animation()
+    b, mats, lts = (Object * 5)(*base), (Material * 7)(*rt.reference_materials()), (Light * 3)(*rt.reference_lights())
+    h = C.c_void_p()
+
+    def create(an, max_frames=1, objs=b, out=C.byref(h)):
+        return lib.rt_anim_create(gpu_ctx.handle, objs, an, 5, mats, 7, lts, 3, max_frames, out)
+
+    a = (ObjectAnim * 5)(*anim)
+    for mf in (0, -1, abi.RT_MAX_BATCH + 1):
+        assert create(a, mf) == abi.RT_ERR_INVALID
+    assert create(None) == abi.RT_ERR_INVALID
+    assert create(a, 1, None) == abi.RT_ERR_INVALID
+    assert create(a, 1, b, None) == abi.RT_ERR_INVALID
+    bad = (ObjectAnim * 5)(*anim)
+    bad[2].position[1].kind = 5
+    assert create(bad) == abi.RT_ERR_INVALID
+    sph = (ObjectAnim * 5)(*anim)
+    sph[4].position[0] = AnimChannel(abi.RT_ANIM_SIN, 1.0, 1.0, 0.0)  # object 4 is the sphere
+    assert create(sph) == abi.RT_ERR_UNSUPPORTED
+    assert b"box" in lib.rt_last_error()
+    assert not h.value
+    # a position that grows with time: laid out for |time| <= 1e4
+    far = (ObjectAnim * 5)(*anim)
+    far[3].position[0] = AnimChannel(abi.RT_ANIM_RATE, 0.0, 0.001, 0.0)
+    assert create(far) == abi.RT_OK
+    out = np.zeros((4, 4, 4), np.float32)
+    try:
+        assert lib.rt_render_animated(gpu_ctx.handle, h, None, 2.0e4, 4, 4, 0, 0, 4, out.ctypes.data, 0,
+                                      None) == abi.RT_ERR_UNSUPPORTED
+        assert lib.rt_render_animated(gpu_ctx.handle, h, None, 1.0, 4, 4, 0, 0, 4, out.ctypes.data, 0, None) == abi.RT_OK
+        assert lib.rt_render_animated(gpu_ctx.handle, h, None, 1.0, 4, 4, 0, 2, 2, out.ctypes.data, 0,
+                                      None) == abi.RT_ERR_INVALID
+        assert lib.rt_render_animated(gpu_ctx.handle, h, None, 1.0, 4, 4, rt.RT_MAX_DEPTH + 1, 0, 4, out.ctypes.data, 0,
+                                      None) == abi.RT_ERR_UNSUPPORTED
+        assert lib.rt_render_batch_animated(gpu_ctx.handle, h, None, None, 1, 4, 4, 0, 8, 1, 0, out.ctypes.data,
+                                            None) == abi.RT_ERR_INVALID
+    finally:
+        lib.rt_anim_destroy(h)

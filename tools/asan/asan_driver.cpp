@@ -17,7 +17,8 @@
 
 namespace rtamd {
 int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int n_mats, const rt_light *lights,
-                int n_lights, std::vector<float4> &blob, DeviceScene &ds, bool with_origin_lists);
+                int n_lights, std::vector<float4> &blob, DeviceScene &ds, bool with_origin_lists,
+                double extent_floor = 0.0);
 int build_origin_lists_for(const std::vector<float4> &host, const DeviceScene &ds, std::vector<uint8_t> &olist);
 }  // namespace rtamd
 
@@ -86,6 +87,13 @@ int main(int argc, char **argv) {
             return 1;
         rt_view v;
         rt_make_view(nullptr, t, &v);
+        // the same objects from the channel form (include/rt.h, rt_animate_objects)
+        rt_object base[RT_REFERENCE_OBJECTS], anim_out[RT_REFERENCE_OBJECTS];
+        rt_object_anim anim[RT_REFERENCE_OBJECTS];
+        if (rt_reference_animation(base, anim) != RT_OK ||
+            rt_animate_objects(base, anim, RT_REFERENCE_OBJECTS, t, anim_out) != RT_OK ||
+            std::memcmp(anim_out, ref, sizeof ref) != 0)
+            return 1;
     }
     for (int n : {0, 1, 16, 17, 33, 64, 65, 256, 257, RT_MAX_OBJECTS - 1}) {
         std::vector<rt_object> objs(n + 1);

@@ -13,7 +13,8 @@
 
 namespace rtamd {
 int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int n_mats, const rt_light *lights,
-                int n_lights, std::vector<float4> &blob, DeviceScene &ds, bool with_origin_lists);
+                int n_lights, std::vector<float4> &blob, DeviceScene &ds, bool with_origin_lists,
+                double extent_floor = 0.0);
 int build_origin_lists_for(const std::vector<float4> &host, const DeviceScene &ds, std::vector<uint8_t> &olist);
 }
 

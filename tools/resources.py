@@ -4,7 +4,7 @@
     python tools/resources.py --gate BASE.so VARIANT.so   exit 1 if VARIANT spills more
     python tools/resources.py --markdown [BUILD]          DESIGN.md §3's occupancy table
 
-Reads the gfx950 code object out of the library's .hip_fatbin section
+Reads the gfx950 code objects out of the library's .hip_fatbin section
 (llvm-objcopy + clang-offload-bundler) and its kernel metadata notes
 (llvm-readelf --notes): .vgpr_count, .sgpr_count and
 .private_segment_fixed_size (scratch bytes per lane) — the numbers the
@@ -56,6 +56,8 @@ def kernel_name(mangled):
         if launch != "0":
             name += ",%s" % launch
         return name + ">"
+    if "animate_kernel" in mangled:
+        return "animate_kernel"
     return mangled
 
 
@@ -65,10 +67,19 @@ def resources(so):
         fb, co = os.path.join(d, "fb.bin"), os.path.join(d, "k.co")
         subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fb, so, os.path.join(d, "x")],
                        check=True, capture_output=True)
-        subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fb,
-                        "--targets=" + TARGET, "--output=" + co], check=True, capture_output=True)
-        notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", co], check=True, capture_output=True,
-                               text=True).stdout
+        # one bundle per translation unit with kernels, back to back in the section
+        with open(fb, "rb") as f:
+            data = f.read()
+        magic, notes = b"__CLANG_OFFLOAD_BUNDLE__", ""
+        starts = [m.start() for m in re.finditer(re.escape(magic), data)]
+        for i, at in enumerate(starts):
+            part = os.path.join(d, "fb%d.bin" % i)
+            with open(part, "wb") as f:
+                f.write(data[at:starts[i + 1] if i + 1 < len(starts) else len(data)])
+            subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + part,
+                            "--targets=" + TARGET, "--output=" + co], check=True, capture_output=True)
+            notes += subprocess.run([LLVM + "/llvm-readelf", "--notes", co], check=True, capture_output=True,
+                                    text=True).stdout
     out, cur = {}, {}
     for line in notes.splitlines():
         m = re.match(r"\s*-?\s*\.(name|vgpr_count|sgpr_count|private_segment_fixed_size):\s+(\S+)", line)
@@ -82,7 +93,7 @@ def resources(so):
     for r in out.values():
         if "vgpr" in r:
             r["waves_per_simd"] = min(8, 512 // max(8, -(-r["vgpr"] // 8) * 8))
-    return {k: v for k, v in out.items() if k.startswith("render_kernel")}
+    return {k: v for k, v in out.items() if k.startswith(("render_kernel", "animate_kernel"))}
 
 
 def fmt(name, r):
@@ -127,6 +138,7 @@ TABLE = [
     ("depth 2, general", "render_kernel<2,false,false>"),
     ("depth 4, config 4 (room, wide masks, origin lists)", "render_kernel<4,false,false,48>"),
     ("depth 4, general", "render_kernel<4,false,false>"),
+    ("the animate kernel (one work-group per frame ahead of an animated render, rt_anim.hip)", "animate_kernel"),
 ]
 
 
