@@ -61,7 +61,7 @@ constexpr float kAnimTimeBound = 1.0e4f;
 // every section 16-B aligned.
 struct AnimTable {
     int32_t n_boxes, n_lights, n_live;
-    int32_t dmask_n, dmask_bytes, dmask_box;  // the slots' LDS direction masks (DeviceScene)
+    int32_t dmask_n, dmask_bytes, dmask_box;  // the slots' LDS direction masks (SceneLayout)
     int32_t n_spheres;
     int32_t finite;     // 1: every time-independent field the plane test looks at is finite
     double extent;      // bound of the scene's extent over the supported times (rt_scene.cpp objects_extent)
@@ -80,7 +80,7 @@ struct AnimParams {
     unsigned char *blobs;      // slot s at blobs + s * slot_bytes
     unsigned long long slot_bytes;
     int32_t first_slot, n_slots;
-    int32_t off_boxes, off_bplane, off_dmask;  // 16-B units in a slot (DeviceScene)
+    int32_t off_boxes, off_bplane, off_dmask;  // 16-B units in a slot (SceneLayout)
     int32_t pad;
     float times[RT_MAX_BATCH];
 };

@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <memory>
 #include <string>
@@ -194,36 +195,59 @@ constexpr int kMaxViewConsts = 256;
 // Largest LDS a work-group may request on gfx950 (160 KiB).
 constexpr size_t kMaxLds = 160 * 1024;
 
+// The layout of a scene blob: its sections' offsets in 16-B units, the mask
+// parameters and the counts. The single definition: build_scene fills it, the
+// host's frame constants and the kernels read it (LaunchParams::layout), and
+// two scenes may share a launch when theirs are equal (rt_render_batch_scenes).
+// All int32 and nothing else, so equality is a comparison of the bytes.
+struct SceneLayout {
+    int32_t off_spheres, off_smeta, off_boxes, off_mats, off_lights, off_lightmat;
+    int32_t off_bvh, n_bvh;  // sphere BVH nodes (2 x float4 each), offset / count
+    int32_t off_blink;       // n_bvh x kBvhOctants uint32 traversal links
+    int32_t off_cone;        // n_lights x n_spheres ShadowCone; -1: none
+                             // (kept only while the LDS total stays within kConeLdsBudget)
+    int32_t off_dmask, dmask_n;  // shadow direction masks (live lights x 6 x n x n); -1: none
+    int32_t dmask_bytes;         // bytes per mask: 2, 4 or 8 (at most 16, 32, 64 mask bits; 4 without masks)
+    int32_t off_gmask, gmask_words;  // wide masks in the blob past blob_units (not staged); -1: none
+    int32_t off_glist;               // their candidate lists (kGListMax); -1: none
+    int32_t blob_units;      // the part every work-group stages into LDS
+    // secondary rays' origin-sphere candidate lists (kOListSlots); -1: none,
+    // or not built yet (ensure_origin_lists)
+    int32_t off_olist;
+    // 1: the LDS direction masks carry a bit per box (bit n_spheres + b)
+    int32_t dmask_box;
+    // per (box, light) a plane that separates the box from the light's end
+    // of every shadow segment (rt_scene.cpp), n_boxes x n_lights float4; -1: none
+    int32_t off_bplane;
+    int32_t n_spheres, n_boxes, n_mats, n_lights;
+};
+
 struct LaunchParams {
     FrameView view[kMaxViews];
     int32_t n_views;
     int32_t width, height;
     int32_t row_begin, n_rows;          // contiguous band [row_begin, row_begin+n_rows)
     int32_t block_rows, n_shards, shard;  // interleaved shard mapping when n_shards > 0
-    int32_t n_spheres, n_boxes, n_mats, n_lights;
     const void *scene;  // device blob
     float4 *out;        // n_views x n_rows x width float4
-    int32_t off_spheres, off_smeta, off_boxes, off_mats, off_lights, off_lightmat;  // 16-B units
-    int32_t off_bvh, n_bvh;  // sphere BVH nodes (2 x float4 each), 16-B units / count
-    int32_t off_blink;       // n_bvh x kBvhOctants uint32 traversal links, 16-B units
-    int32_t off_cone;        // n_lights x n_spheres ShadowCone, 16-B units; -1: none
-                             // (kept only while the LDS total stays within kConeLdsBudget)
-    int32_t off_dmask, dmask_n;  // shadow direction masks (live lights x 6 x n x n), 16-B units; -1: none
-    int32_t dmask_bytes;         // bytes per mask: 2, 4 or 8 (at most 16, 32, 64 spheres)
-    int32_t off_gmask, gmask_words;  // wide masks in the blob past blob_units (not staged), 16-B units; -1: none
-    int32_t off_glist;               // their candidate lists (kGListMax), 16-B units; -1: none
-    int32_t blob_units;      // blob size, 16-B units
     // Monte-Carlo accumulation (render_kernel<D, true>): samples
     // [sample0, sample0 + spp) per pixel, jittered inside the pixel when
     // jitter != 0, summed in sample order and added to out.
     int32_t spp, sample0, jitter;
     uint32_t seed;
+    // The layout of `scene`, and of every view's own blob. It sits behind
+    // `seed` for the persistent kernel, which reads the arguments again per
+    // tile: the compiler merges neighbouring scalar loads into wider ones from
+    // wherever a run of loaded words begins. Here the first four offsets lie on
+    // a 16-B boundary, and no word a depth-0 tile reads comes right before the
+    // offsets or right after the counts. (With the counts first and the layout
+    // ahead of the pointers the kernel read n_lights and three offsets in one
+    // unaligned 16-B load and took one load more per tile.)
+    SceneLayout layout;
     // Queued work distribution (rt_kernel.hip, render_kernel): the counters of
-    // this launch (kSchedInts zeroed ints, left zeroed by the kernel), and the
-    // compute units the resident grid is sized for. nullptr: one work-group
-    // per tile.
+    // this launch (kSchedInts zeroed ints, left zeroed by the kernel).
+    // nullptr: one work-group per tile.
     int32_t *sched;
-    int32_t n_cu;
     int32_t out_format;  // RT_OUTPUT_*: float4, GL_RGBA8 unorm bytes (uchar4) or packed float3 per pixel
     // Each view's per-frame constants ([sphere camera terms][sphere pixel
     // footprints][box camera terms], the LDS image the kernel's frame_setup
@@ -242,38 +266,33 @@ struct LaunchParams {
     // arrays above
     const FrameView *views_dev;
     const float4 *consts_dev;
+    // (last: kernarg_probe reads the block's end)
     float4 frame_consts[kMaxFrameConsts];
-    // secondary rays' origin-sphere candidate lists (kOListSlots), 16-B units;
-    // -1: none (last: the depth-0/1 kernels, which never read it, keep their
-    // argument layout)
-    int32_t off_olist;
-    // 1: the LDS direction masks carry a bit per box (bit n_spheres + b)
-    int32_t dmask_box;
-    // per (box, light) a plane that separates the box from the light's end
-    // of every shadow segment (rt_scene.cpp), 16-B units; -1: none
-    int32_t off_bplane;
-    // host only (the kernels never read it): 1 when every view of the launch
-    // culls, so the depth-0 kernels may take the scene's shape (scene_shape)
-    int32_t shape_cull;
-    int32_t scene_room;  // host only: every scene of the launch is a room (DeviceScene::room)
-    // 1 (set by launch_kernel for the wide-shape recursive kernels): a view's
-    // records in LDS are its footprints and box terms only, not the spheres'
-    // camera terms (the primary rays compute them as secondary rays do: the
-    // same arithmetic, so the same values) — 16 B less per sphere per view
-    int32_t lean_views;
-    // host only: RT_OPT_LAUNCH_SHAPES, the depth-0 shaped kernels may take the
-    // launch's shape (launch_shape)
-    int32_t shape_launch;
-    // host only: RT_OPT_PERSISTENT0 (0 off, 1 automatic, k >= 8: forced, at
-    // most k work-groups; persistent_groups), 0 too when a view of the batch
-    // carries a scene blob of its own (rt_render_batch_scenes). (In the
-    // block's tail padding: the argument block keeps its size.)
-    int32_t persistent0;
 };
-static_assert(sizeof(LaunchParams) == 5808, "kernel argument block: the hidden arguments' offsets");
+static_assert(sizeof(LaunchParams) == 5776, "kernel argument block: the hidden arguments' offsets");
+static_assert(offsetof(LaunchParams, layout) % 16 == 0, "the layout's offsets: aligned scalar loads (see above)");
+static_assert(offsetof(LaunchParams, frame_consts) + sizeof(LaunchParams::frame_consts) == sizeof(LaunchParams),
+              "kernarg_probe reads the last record: nothing the kernels read lies behind it");
 // ROCm passes kernel arguments above 4 KiB (an 8 KB argument block checked on
 // MI355X); this block stays under 6 KiB.
 static_assert(sizeof(LaunchParams) <= 6144, "kernel argument block");
+// What the host decides a launch's kernel and grid from, beside the argument
+// block (no kernel reads it): base_params fills it from the context and the
+// scene, scene_shape / launch_shape / persistent_groups read it.
+struct LaunchHost {
+    // 1 when every view of the launch culls (and RT_OPT_SCENE_SHAPES is on),
+    // so the kernels may take the scene's shape (scene_shape)
+    int32_t shape_cull;
+    int32_t scene_room;  // every scene of the launch is a room (DeviceScene::room)
+    // RT_OPT_LAUNCH_SHAPES: the depth-0 shaped kernels may take the launch's
+    // shape (launch_shape)
+    int32_t shape_launch;
+    // RT_OPT_PERSISTENT0 (0 off, 1 automatic, k >= 8: forced, at most k
+    // work-groups; persistent_groups), 0 too when a view of the batch carries
+    // a scene blob of its own (rt_render_batch_scenes)
+    int32_t persistent0;
+    int32_t n_cu;  // the compute units a resident grid is sized for; 0: tiled launches only
+};
 // Scene shapes (render_kernel<D, ..., kShape>): the scene's features that
 // decide the path a ray takes, as compile-time constants, so the kernel
 // carries none of their run-time tests. Depth 0: the LDS direction masks'
@@ -287,7 +306,7 @@ constexpr int kShapeMaskBytes = 15;
 constexpr int kShapeMaskTexels = 12;  // the LDS masks' texels per face edge in a depth-0 shape (rt_scene.cpp picks 12 where it fits)
 constexpr int kShapeRoom = 16;
 constexpr int kShapeWide = 32;
-int scene_shape(const LaunchParams &p, int max_depth);
+int scene_shape(const SceneLayout &L, const LaunchHost &h, int max_depth);
 // Launch shapes (render_kernel<D, ..., kShape, kLaunch>, the depth-0 shaped
 // kernels without accumulation): the launch's own uniform answers as
 // compile-time constants, a bit per shape; 0: everything read at run time.
@@ -296,14 +315,14 @@ int scene_shape(const LaunchParams &p, int max_depth);
 // n_rows = height, one slice), the RGBA32F surface, cam_short = 1, the host's
 // frame constants present, width and height >= 2. Chosen per launch on the
 // host (launch_shape) from the parameters alone; RT_OPT_LAUNCH_SHAPES 0
-// (LaunchParams::shape_launch) forces 0.
+// (LaunchHost::shape_launch) forces 0.
 constexpr int kLaunchPlain = 1;
 // kLaunchPersistent (only with kLaunchPlain, on the device-view kernels): the
 // resident-grid distribution of a depth-0 batch of one scene (rt_kernel.hip,
 // "Work distribution"). Needs the kernel's resident work-groups, so
 // launch_shape reports it only for a launch whose `resident` is known.
 constexpr int kLaunchPersistent = 2;
-int launch_shape(const LaunchParams &p, int max_depth, int resident = 0);
+int launch_shape(const LaunchParams &p, const LaunchHost &h, int max_depth, int resident = 0);
 // Wave tiles a persistent wave takes per dequeue in the bulk of the launch
 // (kChunk0 consecutive items, view-major; a power of two): 256 frames of 1080p
 // need about 1,300 tiles per microsecond and one counter serves about 88
@@ -362,12 +381,15 @@ __host__ __device__ inline ChunkRange persistent_chunk(int c, int total, int wav
 constexpr int kPersistentMinTilesPerWave = 192;
 // Work-groups of the persistent grid for a plain depth-0 launch on a kernel
 // with `resident` resident work-groups on the device, 0: the tiled launch.
-int persistent_groups(const LaunchParams &p, int resident);
-// Lean views (LaunchParams::lean_views): the wide-shape kernels.
+int persistent_groups(const LaunchParams &p, const LaunchHost &h, int resident);
+// Lean views (the wide-shape recursive kernels): a view's records in LDS are
+// its footprints and box terms only, not the spheres' camera terms (the
+// primary rays compute them as secondary rays do: the same arithmetic, so the
+// same values) — 16 B less per sphere per view.
 constexpr bool kLeanViews(int shape) { return (shape & kShapeWide) != 0; }
 // 16-B records of one view's per-frame constants in LDS: the spheres' camera
 // terms (not with lean views) and footprints, the boxes' camera terms.
-inline int view_units(const LaunchParams &p) { return (p.lean_views ? 1 : 2) * p.n_spheres + p.n_boxes; }
+inline int view_units(const SceneLayout &L, bool lean) { return (lean ? 1 : 2) * L.n_spheres + L.n_boxes; }
 constexpr int kQueues = 32;                            // wave-tile queues of a queued launch
 constexpr int kQueueStride = 64;                       // ints: each counter on a 256-B line of its own
 constexpr int kSchedInts = 2 * kQueues * kQueueStride; // heads + done counters of one launch
@@ -400,16 +422,8 @@ __host__ __device__ inline int persistent_first_chunk(int g) { return (g & ~(kQu
 
 struct DeviceScene {
     void *blob = nullptr;
-    int32_t blob_units = 0;
-    int32_t off_spheres = 0, off_smeta = 0, off_boxes = 0, off_mats = 0, off_lights = 0, off_lightmat = 0;
-    int32_t off_bvh = 0, n_bvh = 0, off_blink = 0, off_cone = 0;
-    int32_t off_dmask = -1, dmask_n = 0, dmask_bytes = 4;
-    int32_t dmask_box = 0;  // the LDS masks carry a bit per box, bit n_spheres + b (round 6)
-    int32_t off_bplane = -1;  // n_boxes x n_lights separating planes (float4), 16-B units; -1: none (round 6)
-    int32_t off_gmask = -1, gmask_words = 0, off_glist = -1;
-    int32_t off_olist = -1;   // -1 until the lists are built (ensure_origin_lists)
+    SceneLayout layout{};  // (off_olist -1 until the lists are built: ensure_origin_lists)
     int32_t olist_eligible = 0;  // kOListMinSpheres..256 spheres: depth >= 2 renders get the lists
-    int32_t n_spheres = 0, n_boxes = 0, n_mats = 0, n_lights = 0;
     // 1: the one box is a room: translate-only, every live light strictly
     // inside it (the shadow queries' box shortcut always applies; kShapeRoom)
     int32_t room = 0;
@@ -442,12 +456,13 @@ void reference_box_transforms(const float pos[3], const float ang[3], float l2w[
 
 // rt_kernel.hip. Clears p.sched when the launch does not use the queued
 // distribution (so the caller knows whether the counter slot is in use).
-hipError_t launch_render(LaunchParams &p, int max_depth, hipStream_t stream);
-size_t lds_bytes(const LaunchParams &p);
+hipError_t launch_render(LaunchParams &p, const LaunchHost &h, int max_depth, hipStream_t stream);
+// LDS of a one-view work-group: the blob's staged part and the view's records.
+size_t lds_bytes(const SceneLayout &L, bool lean = false);
 // Views of one scene a queued launch at this depth holds (deep frames: every
 // view's per-frame constants beside the scene in LDS at the one-view
 // launch's occupancy), 1..kMaxViews; 1 below the queued depths.
-int queued_views(const LaunchParams &p, int max_depth);
+int queued_views(const SceneLayout &L, int max_depth);
 // Self-test of the kernel argument block on the context's stream (rt_create).
 int check_kernarg_block(hipStream_t stream);
 
@@ -469,11 +484,12 @@ struct UseEvent {
     }
 };
 int check_render_args(const rt_context *ctx, const rt_scene *scene, int width, int height, int max_depth);
-// launch parameters of n_views views of `scene` on `ctx` (output and rows left to the caller)
+// launch parameters of n_views views of `scene` on `ctx` (output and rows left
+// to the caller) and, in h, the host's side of the launch decisions
 LaunchParams base_params(const rt_context *ctx, const rt_scene *scene, const rt_view *views, int n_views,
-                         int width, int height);
+                         int width, int height, LaunchHost &h);
 // launch on `stream` with the context's queue slot and kernel-time events
-int launch(rt_context *ctx, LaunchParams &p, int max_depth, hipStream_t stream);
+int launch(rt_context *ctx, LaunchParams &p, const LaunchHost &h, int max_depth, hipStream_t stream);
 // Before a render at max_depth: a scene that reads origin-sphere lists at
 // this depth (max_depth >= 2, RT_OPT_ORIGIN_LISTS on, 33-256 spheres) gets
 // them built and appended to its device blob the first time (the region past
@@ -487,6 +503,9 @@ int ensure_origin_lists(rt_context *ctx, const rt_scene *scene, int max_depth);
 // by the first scene noted, then reused for the call's other scenes); nullptr:
 // an event of this call alone
 int note_scene_use(const rt_scene *scene, hipStream_t stream, std::shared_ptr<UseEvent> *shared = nullptr);
+// a render call's launch of views of one scene: launch, then note_scene_use
+int launch_scene(rt_context *ctx, const rt_scene *scene, LaunchParams &p, const LaunchHost &h, int max_depth,
+                 hipStream_t stream);
 // bytes per pixel of a surface format (RT_OUTPUT_*)
 inline size_t surface_bytes(int fmt) { return fmt == RT_OUTPUT_RGBA8 ? 4 : (fmt == RT_OUTPUT_RGB32F ? 12 : 16); }
 

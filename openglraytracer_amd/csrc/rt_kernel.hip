@@ -1744,10 +1744,10 @@ __device__ __forceinline__ void frame_setup(const LaunchParams &p, const FrameVi
     const int hw = p.width / 2, hh = p.height / 2;
     const bool cull = V.cull && hw > 0 && hh > 0;
     const float *P = V.proj;
-    for (int item = threadIdx.x; item < 8 * p.n_spheres; item += kThreads) {  // whole groups of 8 lanes
+    for (int item = threadIdx.x; item < 8 * p.layout.n_spheres; item += kThreads) {  // whole groups of 8 lanes
         const int s = item >> 3, i = item & 7;
-        const float4 c = blob[p.off_spheres + s];
-        const float rad = __int_as_float(reinterpret_cast<const int4 *>(blob + p.off_smeta)[s].z);
+        const float4 c = blob[p.layout.off_spheres + s];
+        const float rad = __int_as_float(reinterpret_cast<const int4 *>(blob + p.layout.off_smeta)[s].z);
         // corner i of the (inflated) bounding cube, projected with proj*view
         const float r = rad * 1.001f + 1e-3f;
         const float X = c.x + ((i & 1) ? r : -r), Y = c.y + ((i & 2) ? r : -r), Z = c.z + ((i & 4) ? r : -r);
@@ -1772,8 +1772,8 @@ __device__ __forceinline__ void frame_setup(const LaunchParams &p, const FrameVi
                                           : make_int4(INT_MIN / 2, INT_MAX / 2, INT_MIN / 2, INT_MAX / 2);
         }
     }
-    const BoxRec *box = reinterpret_cast<const BoxRec *>(blob + p.off_boxes);
-    for (int b = threadIdx.x; b < p.n_boxes; b += kThreads) {
+    const BoxRec *box = reinterpret_cast<const BoxRec *>(blob + p.layout.off_boxes);
+    for (int b = threadIdx.x; b < p.layout.n_boxes; b += kThreads) {
         const v3 rs = xform_point(box[b].w2l, origin);
         box_cam[b] = make_float4(rs.x, rs.y, rs.z, strictly_inside(box[b], rs) ? 1.0f : 0.0f);
     }
@@ -2021,7 +2021,7 @@ __device__ __forceinline__ const LaunchParams &launch_args() {
 }
 // The wave's slot of view records in LDS, after the scene.
 __device__ __forceinline__ float4 *persistent_slot(const LaunchParams &p, float4 *lds) {
-    return lds + p.blob_units + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * p.n_frame_consts;
+    return lds + p.layout.blob_units + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * p.n_frame_consts;
 }
 // View z's records into the wave's slot. The fences order the refill between
 // the previous tile's reads and the next tile's: one wave, in-order LDS.
@@ -2042,39 +2042,47 @@ template <int kShape, int kLaunch>
 __device__ __forceinline__ void persistent_tile(const LaunchParams &p, float4 *lds, int z, int wx, int wy) {
     const float4 *blob = static_cast<const float4 *>(p.scene);
     float4 *const slot = persistent_slot(p, lds);
+    // (The Scene view is written out here and in render_kernel, field by field
+    // in one order. Built by one inlined helper that the callers completed
+    // with their view records, the same values reached the compiler in another
+    // order and this kernel's per-tile scalar code was scheduled differently:
+    // same registers, same frames, but config 2 at 256 views was slower in
+    // every alternating round, medians 6.266 -> 6.275 ms, 0.15 %,
+    // profiles/r11a_bench_alternating.log section 3.)
+    const SceneLayout &L = p.layout;
     Scene S;
-    S.sph = lds + p.off_spheres;
-    S.smeta = reinterpret_cast<const int4 *>(lds + p.off_smeta);
+    S.sph = lds + L.off_spheres;
+    S.smeta = reinterpret_cast<const int4 *>(lds + L.off_smeta);
     S.sph_cam = slot;
-    S.sph_px = reinterpret_cast<const int4 *>(slot + p.n_spheres);
-    S.box = reinterpret_cast<const BoxRec *>(lds + p.off_boxes);
-    S.box_cam = slot + 2 * p.n_spheres;
-    S.mat = reinterpret_cast<const MatRec *>(lds + p.off_mats);
-    S.light = reinterpret_cast<const LightRec *>(lds + p.off_lights);
-    S.lm = reinterpret_cast<const LightMatRec *>(lds + p.off_lightmat);
-    S.bvh = lds + p.off_bvh;
-    S.blink = reinterpret_cast<const uint32_t *>(lds + p.off_blink);
+    S.sph_px = reinterpret_cast<const int4 *>(slot + L.n_spheres);
+    S.box = reinterpret_cast<const BoxRec *>(lds + L.off_boxes);
+    S.box_cam = slot + 2 * L.n_spheres;
+    S.mat = reinterpret_cast<const MatRec *>(lds + L.off_mats);
+    S.light = reinterpret_cast<const LightRec *>(lds + L.off_lights);
+    S.lm = reinterpret_cast<const LightMatRec *>(lds + L.off_lightmat);
+    S.bvh = lds + L.off_bvh;
+    S.blink = reinterpret_cast<const uint32_t *>(lds + L.off_blink);
     S.cone = nullptr;  // (a depth-0 mask shape: render_wave_tile sets the rest of the shape)
-    S.dmask = reinterpret_cast<const char *>(lds + p.off_dmask);
+    S.dmask = reinterpret_cast<const char *>(lds + L.off_dmask);
     S.dmask_n = kShapeMaskTexels;
     S.dmask_bytes = kShape & kShapeMaskBytes;
-    S.dmask_box = p.dmask_box;
-    S.cbplane = p.off_bplane >= 0 ? (const __attribute__((address_space(4))) float4 *)(blob + p.off_bplane) : nullptr;
+    S.dmask_box = L.dmask_box;
+    S.cbplane = L.off_bplane >= 0 ? (const __attribute__((address_space(4))) float4 *)(blob + L.off_bplane) : nullptr;
     S.gmask = nullptr;
     S.gwords = 0;
     S.glist = nullptr;
     S.olist = nullptr;
-    S.cbox = (const __attribute__((address_space(4))) BoxRec *)(blob + p.off_boxes);
-    S.clight = (const __attribute__((address_space(4))) LightRec *)(blob + p.off_lights);
+    S.cbox = (const __attribute__((address_space(4))) BoxRec *)(blob + L.off_boxes);
+    S.clight = (const __attribute__((address_space(4))) LightRec *)(blob + L.off_lights);
 #ifdef RT_UNIFORM_MAT
-    S.cmat = (const __attribute__((address_space(4))) MatRec *)(blob + p.off_mats);
-    S.clm = (const __attribute__((address_space(4))) LightMatRec *)(blob + p.off_lightmat);
+    S.cmat = (const __attribute__((address_space(4))) MatRec *)(blob + L.off_mats);
+    S.clm = (const __attribute__((address_space(4))) LightMatRec *)(blob + L.off_lightmat);
 #endif
     S.nbvh = 0;
-    S.ns = p.n_spheres;
-    S.nb = p.n_boxes;
-    S.nl = p.n_lights;
-    S.nm = p.n_mats;
+    S.ns = L.n_spheres;
+    S.nb = L.n_boxes;
+    S.nl = L.n_lights;
+    S.nm = L.n_mats;
     const FrameView V = cload((const __attribute__((address_space(4))) FrameView *)(p.views_dev) + z);
     const Ray none{mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f)};
     render_wave_tile<0, false, kShape, kLaunch>(p, S, V, wx, wy, z, wave_pixel<kLaunch>(p, wx, wy), none, false);
@@ -2093,7 +2101,7 @@ __device__ __forceinline__ void render_persistent0(float4 *lds) {
     {
         const LaunchParams &p = launch_args();
         const float4 *blob = static_cast<const float4 *>(p.scene);
-        for (int i = threadIdx.x; i < p.blob_units; i += kThreads) lds[i] = blob[i];
+        for (int i = threadIdx.x; i < p.layout.blob_units; i += kThreads) lds[i] = blob[i];
     }
     __syncthreads();
     __builtin_amdgcn_s_setprio(0);
@@ -2214,7 +2222,7 @@ __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchPar
     const float4 *blob = static_cast<const float4 *>(V.blob ? V.blob : p.scene);
     const int tid = threadIdx.x;
     float4 first = make_float4(0.0f, 0.0f, 0.0f, 0.0f), fc = first;
-    if (tid < p.blob_units) first = blob[tid];
+    if (tid < p.layout.blob_units) first = blob[tid];
     // this view's per-frame constants computed on the host (when every
     // view's fit in the kernel arguments: host_frame_setup) — else derived
     // below by every work-group
@@ -2222,12 +2230,12 @@ __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchPar
     // lean views (the wide shapes, kLeanViews): the host's records of a view
     // minus their first n_spheres (the camera terms) go to LDS
     constexpr bool kLean = kLeanViews(kShape);
-    const int skip = kLean ? p.n_spheres : 0, keep = p.n_frame_consts - skip;
+    const int skip = kLean ? p.layout.n_spheres : 0, keep = p.n_frame_consts - skip;
     if (tid < keep) fc = (kDev ? p.consts_dev : p.frame_consts)[z * p.n_frame_consts + skip + tid];
-    float4 *const views = lds + p.blob_units;  // view k's records at views + k * view_units
+    float4 *const views = lds + p.layout.blob_units;  // view k's records at views + k * view_units
     float4 *sph_cam = kLean ? nullptr : views;
-    int4 *sph_px = reinterpret_cast<int4 *>(views + (kLean ? 0 : p.n_spheres));
-    float4 *box_cam = reinterpret_cast<float4 *>(sph_px + p.n_spheres);
+    int4 *sph_px = reinterpret_cast<int4 *>(views + (kLean ? 0 : p.layout.n_spheres));
+    float4 *box_cam = reinterpret_cast<float4 *>(sph_px + p.layout.n_spheres);
     const int own_wx = static_cast<int>(blockIdx.x) * kWavesX + wave % kWavesX;
     const int own_wy = static_cast<int>(blockIdx.y) * kWavesY + wave / kWavesX;
     const Pixel own = wave_pixel<kLaunch>(p, own_wx, own_wy);
@@ -2236,10 +2244,10 @@ __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchPar
     if (!queued && !kAccum) own_ray = camera_ray<kLaunch>(p, V, own.x, own.y, 0.0f, 0.0f);
     RT_PHASE_AFTER(15, own_ray.dir.x + own_ray.dir.y + own_ray.dir.z);
     RT_PHASE(10);
-    if (tid < p.blob_units) lds[tid] = first;
+    if (tid < p.layout.blob_units) lds[tid] = first;
     RT_PHASE(11);
-    for (int i = tid + kThreads; i < p.blob_units; i += kThreads) lds[i] = blob[i];
-    const int view_units = (kLean ? 1 : 2) * p.n_spheres + p.n_boxes;
+    for (int i = tid + kThreads; i < p.layout.blob_units; i += kThreads) lds[i] = blob[i];
+    const int view_units = (kLean ? 1 : 2) * p.layout.n_spheres + p.layout.n_boxes;
     if (kPlain || p.n_frame_consts > 0) {  // (a plain launch carries the host's records)
         if (tid < keep) views[tid] = fc;
         if (kLean) {
@@ -2255,8 +2263,8 @@ __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchPar
         frame_setup(p, V, sph_cam, sph_px, box_cam);
         for (int k = 1; k < n_staged; ++k) {
             float4 *c = views + k * view_units;
-            int4 *px = reinterpret_cast<int4 *>(c + (kLean ? 0 : p.n_spheres));
-            frame_setup(p, p.view[k], kLean ? nullptr : c, px, reinterpret_cast<float4 *>(px + p.n_spheres));
+            int4 *px = reinterpret_cast<int4 *>(c + (kLean ? 0 : p.layout.n_spheres));
+            frame_setup(p, p.view[k], kLean ? nullptr : c, px, reinterpret_cast<float4 *>(px + p.layout.n_spheres));
         }
     }
     RT_PHASE(12);
@@ -2270,41 +2278,42 @@ __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchPar
     __syncthreads();
     __builtin_amdgcn_s_setprio(0);
     RT_PHASE(13);
+    const SceneLayout &L = p.layout;
     Scene S;
-    S.sph = lds + p.off_spheres;
-    S.smeta = reinterpret_cast<const int4 *>(lds + p.off_smeta);
+    S.sph = lds + L.off_spheres;
+    S.smeta = reinterpret_cast<const int4 *>(lds + L.off_smeta);
     S.sph_cam = sph_cam;
     S.sph_px = sph_px;
-    S.box = reinterpret_cast<const BoxRec *>(lds + p.off_boxes);
+    S.box = reinterpret_cast<const BoxRec *>(lds + L.off_boxes);
     S.box_cam = box_cam;
-    S.mat = reinterpret_cast<const MatRec *>(lds + p.off_mats);
-    S.light = reinterpret_cast<const LightRec *>(lds + p.off_lights);
-    S.lm = reinterpret_cast<const LightMatRec *>(lds + p.off_lightmat);
-    S.bvh = lds + p.off_bvh;
-    S.blink = reinterpret_cast<const uint32_t *>(lds + p.off_blink);
-    S.cone = p.off_cone >= 0 ? reinterpret_cast<const ShadowCone *>(lds + p.off_cone) : nullptr;
-    S.dmask = p.off_dmask >= 0 ? reinterpret_cast<const char *>(lds + p.off_dmask) : nullptr;
-    S.dmask_n = p.dmask_n;
-    S.dmask_bytes = p.dmask_bytes;
-    S.dmask_box = p.dmask_box;
-    S.cbplane = p.off_bplane >= 0 ? (const __attribute__((address_space(4))) float4 *)(blob + p.off_bplane) : nullptr;
+    S.mat = reinterpret_cast<const MatRec *>(lds + L.off_mats);
+    S.light = reinterpret_cast<const LightRec *>(lds + L.off_lights);
+    S.lm = reinterpret_cast<const LightMatRec *>(lds + L.off_lightmat);
+    S.bvh = lds + L.off_bvh;
+    S.blink = reinterpret_cast<const uint32_t *>(lds + L.off_blink);
+    S.cone = L.off_cone >= 0 ? reinterpret_cast<const ShadowCone *>(lds + L.off_cone) : nullptr;
+    S.dmask = L.off_dmask >= 0 ? reinterpret_cast<const char *>(lds + L.off_dmask) : nullptr;
+    S.dmask_n = L.dmask_n;
+    S.dmask_bytes = L.dmask_bytes;
+    S.dmask_box = L.dmask_box;
+    S.cbplane = L.off_bplane >= 0 ? (const __attribute__((address_space(4))) float4 *)(blob + L.off_bplane) : nullptr;
     // (recursive depths only: the depth-0/1 kernels keep their register
     // budget and use the per-wave cone for such scenes)
-    S.gmask = kDepth >= 2 && p.off_gmask >= 0 ? reinterpret_cast<const uint64_t *>(blob + p.off_gmask) : nullptr;
-    S.gwords = p.gmask_words;
-    S.glist = S.gmask && p.off_glist >= 0 ? reinterpret_cast<const uint4 *>(blob + p.off_glist) : nullptr;
-    S.olist = kDepth >= 2 && p.off_olist >= 0 ? reinterpret_cast<const uint4 *>(blob + p.off_olist) : nullptr;
-    S.cbox = (const __attribute__((address_space(4))) BoxRec *)(blob + p.off_boxes);
-    S.clight = (const __attribute__((address_space(4))) LightRec *)(blob + p.off_lights);
+    S.gmask = kDepth >= 2 && L.off_gmask >= 0 ? reinterpret_cast<const uint64_t *>(blob + L.off_gmask) : nullptr;
+    S.gwords = L.gmask_words;
+    S.glist = S.gmask && L.off_glist >= 0 ? reinterpret_cast<const uint4 *>(blob + L.off_glist) : nullptr;
+    S.olist = kDepth >= 2 && L.off_olist >= 0 ? reinterpret_cast<const uint4 *>(blob + L.off_olist) : nullptr;
+    S.cbox = (const __attribute__((address_space(4))) BoxRec *)(blob + L.off_boxes);
+    S.clight = (const __attribute__((address_space(4))) LightRec *)(blob + L.off_lights);
 #ifdef RT_UNIFORM_MAT
-    S.cmat = (const __attribute__((address_space(4))) MatRec *)(blob + p.off_mats);
-    S.clm = (const __attribute__((address_space(4))) LightMatRec *)(blob + p.off_lightmat);
+    S.cmat = (const __attribute__((address_space(4))) MatRec *)(blob + L.off_mats);
+    S.clm = (const __attribute__((address_space(4))) LightMatRec *)(blob + L.off_lightmat);
 #endif
-    S.nbvh = p.n_bvh;
-    S.ns = p.n_spheres;
-    S.nb = p.n_boxes;
-    S.nl = p.n_lights;
-    S.nm = p.n_mats;
+    S.nbvh = L.n_bvh;
+    S.ns = L.n_spheres;
+    S.nb = L.n_boxes;
+    S.nl = L.n_lights;
+    S.nm = L.n_mats;
     const int wtx = (p.width + 7) / 8;
     const int view_tiles = wtx * (((kPlain ? p.height : p.slice_rows) + 7) / 8);
     const int total = queued ? view_tiles * p.n_views : 1;
@@ -2329,8 +2338,8 @@ __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchPar
         if (queued && zt != 0) {
             const float4 *c = views + zt * view_units;
             St.sph_cam = kLean ? nullptr : c;
-            St.sph_px = reinterpret_cast<const int4 *>(c + (kLean ? 0 : p.n_spheres));
-            St.box_cam = reinterpret_cast<const float4 *>(St.sph_px + p.n_spheres);
+            St.sph_px = reinterpret_cast<const int4 *>(c + (kLean ? 0 : p.layout.n_spheres));
+            St.box_cam = reinterpret_cast<const float4 *>(St.sph_px + p.layout.n_spheres);
         }
         render_wave_tile<kDepth, kAccum, kShape, kLaunch>(p, St, queued ? p.view[zt] : V, wx, wy, zt,
                                                        queued ? wave_pixel<kLaunch>(p, wx, wy) : own, own_ray,
@@ -2376,15 +2385,15 @@ int groups_per_cu(const void *fn, size_t lds) {
 
 // LDS of a queued launch of n views: the scene and every view's per-frame
 // constants.
-size_t queued_lds_bytes(const LaunchParams &p, int n) {
-    return lds_bytes(p) + static_cast<size_t>(n - 1) * view_units(p) * sizeof(float4);
+size_t queued_lds_bytes(const SceneLayout &L, bool lean, int n) {
+    return lds_bytes(L, lean) + static_cast<size_t>(n - 1) * view_units(L, lean) * sizeof(float4);
 }
 
 // Views of one scene a queued launch holds at the one-view launch's resident
 // work-groups per CU (their constants beside the scene in LDS), at most
 // kMaxViews (cached per kernel and scene shape: occupancy queries are host
 // work).
-int queued_views_for(const void *fn, const LaunchParams &p) {
+int queued_views_for(const void *fn, const SceneLayout &L, bool lean) {
     struct Entry {
         const void *fn;
         size_t lds;
@@ -2392,14 +2401,14 @@ int queued_views_for(const void *fn, const LaunchParams &p) {
     };
     thread_local Entry cache[8] = {};
     thread_local int next = 0;
-    const size_t lds = lds_bytes(p);
-    const int units = view_units(p);
+    const size_t lds = lds_bytes(L, lean);
+    const int units = view_units(L, lean);
     for (const Entry &e : cache)
         if (e.fn == fn && e.lds == lds && e.units == units && e.n > 0) return e.n;
     const int g1 = groups_per_cu(fn, lds);
     int n = 1;
-    while (n < kMaxViews && queued_lds_bytes(p, n + 1) <= kMaxLds &&
-           groups_per_cu(fn, queued_lds_bytes(p, n + 1)) >= g1)
+    while (n < kMaxViews && queued_lds_bytes(L, lean, n + 1) <= kMaxLds &&
+           groups_per_cu(fn, queued_lds_bytes(L, lean, n + 1)) >= g1)
         ++n;
     cache[next] = {fn, lds, units, n};
     next = (next + 1) % 8;
@@ -2407,13 +2416,13 @@ int queued_views_for(const void *fn, const LaunchParams &p) {
 }
 
 template <int kDepth, bool kAccum, bool kDev = false, int kShape = 0, int kLaunch = 0>
-hipError_t launch_kernel(LaunchParams &p, hipStream_t stream) {
-    p.lean_views = kLeanViews(kShape) ? 1 : 0;
-    size_t lds = lds_bytes(p);
+hipError_t launch_kernel(LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
+    constexpr bool kLean = kLeanViews(kShape);
+    size_t lds = lds_bytes(p.layout, kLean);
     const void *fn = reinterpret_cast<const void *>(&render_kernel<kDepth, kAccum, kDev, kShape, kLaunch>);
     dim3 grid((p.width + kTileX - 1) / kTileX, (p.slice_rows + kTileY - 1) / kTileY, p.n_views);
     const int wave_tiles = ((p.width + 7) / 8) * ((p.slice_rows + 7) / 8) * p.n_views;
-    const int resident = p.n_cu > 0 ? groups_per_cu(fn, lds) * p.n_cu : 0;
+    const int resident = h.n_cu > 0 ? groups_per_cu(fn, lds) * h.n_cu : 0;
     // queued: more wave tiles than resident waves, every queue has a wave (a
     // queue without one would leave its tiles unrendered), and for several
     // views: one scene (staged once) and every view's constants in LDS at the
@@ -2422,9 +2431,9 @@ hipError_t launch_kernel(LaunchParams &p, hipStream_t stream) {
     for (int k = 0; k < p.n_views && one_scene; ++k) one_scene = p.view[k].blob == nullptr;
     if (kQueuedDepth(kDepth) && p.sched && wave_tiles > resident * (kThreads / 64) &&
         resident * (kThreads / 64) >= kQueues &&
-        (p.n_views == 1 || (one_scene && queued_views_for(fn, p) >= p.n_views))) {
+        (p.n_views == 1 || (one_scene && queued_views_for(fn, p.layout, kLean) >= p.n_views))) {
         grid = dim3(resident, 1, 1);
-        lds = queued_lds_bytes(p, p.n_views);
+        lds = queued_lds_bytes(p.layout, kLean, p.n_views);
     } else {
         p.sched = nullptr;
     }
@@ -2434,7 +2443,7 @@ hipError_t launch_kernel(LaunchParams &p, hipStream_t stream) {
 
 // LDS of a persistent launch: the scene and one view's records per wave.
 size_t persistent_lds_bytes(const LaunchParams &p) {
-    return (static_cast<size_t>(p.blob_units) + static_cast<size_t>(kThreads / 64) * p.n_frame_consts) * sizeof(float4);
+    return (static_cast<size_t>(p.layout.blob_units) + static_cast<size_t>(kThreads / 64) * p.n_frame_consts) * sizeof(float4);
 }
 
 // The depth-0 kernels in the scene's shape (scene_shape): 2-, 4- or 8-byte
@@ -2446,96 +2455,95 @@ size_t persistent_lds_bytes(const LaunchParams &p) {
 // (or RT_OPT_PERSISTENT0's cap), the LDS the scene and a view's records per
 // wave.
 template <bool kAccum, bool kDev, int kShape>
-hipError_t launch_shaped0(LaunchParams &p, hipStream_t stream) {
+hipError_t launch_shaped0(LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
     if constexpr (!kAccum) {
-        if ((launch_shape(p, 0) & kLaunchPlain) != 0) {
+        if ((launch_shape(p, h, 0) & kLaunchPlain) != 0) {
             if constexpr (kDev) {
                 constexpr int kPersistent = kLaunchPlain | kLaunchPersistent;
                 const size_t lds = persistent_lds_bytes(p);
-                if (p.persistent0 > 0 && p.sched && lds <= kMaxLds && p.n_cu > 0) {  // (else: no occupancy query)
+                if (h.persistent0 > 0 && p.sched && lds <= kMaxLds && h.n_cu > 0) {  // (else: no occupancy query)
                     const void *fn = reinterpret_cast<const void *>(&render_kernel<0, false, true, kShape, kPersistent>);
-                    const int groups = persistent_groups(p, groups_per_cu(fn, lds) * p.n_cu);
+                    const int groups = persistent_groups(p, h, groups_per_cu(fn, lds) * h.n_cu);
                     if (groups > 0) {
-                        p.lean_views = 0;
                         hipLaunchKernelGGL((render_kernel<0, false, true, kShape, kPersistent>), dim3(groups),
                                            dim3(kThreads), lds, stream, p);
                         return hipGetLastError();
                     }
                 }
             }
-            return launch_kernel<0, false, kDev, kShape, kLaunchPlain>(p, stream);
+            return launch_kernel<0, false, kDev, kShape, kLaunchPlain>(p, h, stream);
         }
     }
-    return launch_kernel<0, kAccum, kDev, kShape>(p, stream);
+    return launch_kernel<0, kAccum, kDev, kShape>(p, h, stream);
 }
 template <bool kAccum, bool kDev>
-hipError_t launch_depth0(LaunchParams &p, hipStream_t stream) {
-    switch (scene_shape(p, 0)) {
-        case 2: return launch_shaped0<kAccum, kDev, 2>(p, stream);
-        case 4: return launch_shaped0<kAccum, kDev, 4>(p, stream);
-        case 8: return launch_shaped0<kAccum, kDev, 8>(p, stream);
-        case 2 | kShapeRoom: return launch_shaped0<kAccum, kDev, 2 | kShapeRoom>(p, stream);
-        case 4 | kShapeRoom: return launch_shaped0<kAccum, kDev, 4 | kShapeRoom>(p, stream);
-        case 8 | kShapeRoom: return launch_shaped0<kAccum, kDev, 8 | kShapeRoom>(p, stream);
-        default: return launch_kernel<0, kAccum, kDev, 0>(p, stream);
+hipError_t launch_depth0(LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
+    switch (scene_shape(p.layout, h, 0)) {
+        case 2: return launch_shaped0<kAccum, kDev, 2>(p, h, stream);
+        case 4: return launch_shaped0<kAccum, kDev, 4>(p, h, stream);
+        case 8: return launch_shaped0<kAccum, kDev, 8>(p, h, stream);
+        case 2 | kShapeRoom: return launch_shaped0<kAccum, kDev, 2 | kShapeRoom>(p, h, stream);
+        case 4 | kShapeRoom: return launch_shaped0<kAccum, kDev, 4 | kShapeRoom>(p, h, stream);
+        case 8 | kShapeRoom: return launch_shaped0<kAccum, kDev, 8 | kShapeRoom>(p, h, stream);
+        default: return launch_kernel<0, kAccum, kDev, 0>(p, h, stream);
     }
 }
 
 // The recursive kernels in the wide-mask shape (scene_shape), else general.
 template <int kDepth>
-hipError_t launch_deep(LaunchParams &p, hipStream_t stream) {
-    switch (scene_shape(p, kDepth)) {
-        case kShapeWide: return launch_kernel<kDepth, false, false, kShapeWide>(p, stream);
-        case kShapeWide | kShapeRoom: return launch_kernel<kDepth, false, false, kShapeWide | kShapeRoom>(p, stream);
-        default: return launch_kernel<kDepth, false, false, 0>(p, stream);
+hipError_t launch_deep(LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
+    switch (scene_shape(p.layout, h, kDepth)) {
+        case kShapeWide: return launch_kernel<kDepth, false, false, kShapeWide>(p, h, stream);
+        case kShapeWide | kShapeRoom: return launch_kernel<kDepth, false, false, kShapeWide | kShapeRoom>(p, h, stream);
+        default: return launch_kernel<kDepth, false, false, 0>(p, h, stream);
     }
 }
 
 template <int kDepth>
-hipError_t launch_depth(LaunchParams &p, hipStream_t stream) {
+hipError_t launch_depth(LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
     if (p.views_dev) {  // a device-side view batch (render_batch_impl: depth 0-1, no accumulation)
         if constexpr (kDepth == 0) {
-            if (p.spp == 0) return launch_depth0<false, true>(p, stream);
+            if (p.spp == 0) return launch_depth0<false, true>(p, h, stream);
         } else if constexpr (kDepth == 1) {
-            if (p.spp == 0) return launch_kernel<kDepth, false, true>(p, stream);
+            if (p.spp == 0) return launch_kernel<kDepth, false, true>(p, h, stream);
         }
         return hipErrorInvalidValue;
     }
-    if constexpr (kDepth == 0) return p.spp > 0 ? launch_depth0<true, false>(p, stream) : launch_depth0<false, false>(p, stream);
+    if constexpr (kDepth == 0) return p.spp > 0 ? launch_depth0<true, false>(p, h, stream) : launch_depth0<false, false>(p, h, stream);
     if constexpr (kDepth >= 2) {
-        if (p.spp == 0) return launch_deep<kDepth>(p, stream);
+        if (p.spp == 0) return launch_deep<kDepth>(p, h, stream);
     }
-    return p.spp > 0 ? launch_kernel<kDepth, true>(p, stream) : launch_kernel<kDepth, false>(p, stream);
+    return p.spp > 0 ? launch_kernel<kDepth, true>(p, h, stream) : launch_kernel<kDepth, false>(p, h, stream);
 }
 
 }  // namespace
 
-int scene_shape(const LaunchParams &p, int max_depth) {
-    if (!p.shape_cull) return 0;  // culling off for a view (or RT_OPT_SCENE_SHAPES 0)
-    const int box = p.n_boxes == 1 && p.scene_room ? kShapeRoom : 0;
+int scene_shape(const SceneLayout &L, const LaunchHost &h, int max_depth) {
+    if (!h.shape_cull) return 0;  // culling off for a view (or RT_OPT_SCENE_SHAPES 0)
+    const int box = L.n_boxes == 1 && h.scene_room ? kShapeRoom : 0;
     if (max_depth == 0) {  // every shadow query walks the LDS masks
-        if (p.off_dmask < 0 || (p.dmask_bytes != 2 && p.dmask_bytes != 4 && p.dmask_bytes != 8) ||
-            p.dmask_n != kShapeMaskTexels)
+        if (L.off_dmask < 0 || (L.dmask_bytes != 2 && L.dmask_bytes != 4 && L.dmask_bytes != 8) ||
+            L.dmask_n != kShapeMaskTexels)
             return 0;
-        return p.dmask_bytes | box;
+        return L.dmask_bytes | box;
     }
     if (max_depth >= 2) {  // the wide masks' lists and the origin-sphere lists take the rays
-        if (p.off_gmask < 0 || p.off_glist < 0 || p.off_olist < 0) return 0;
+        if (L.off_gmask < 0 || L.off_glist < 0 || L.off_olist < 0) return 0;
         return kShapeWide | box;
     }
     return 0;
 }
 
-int persistent_groups(const LaunchParams &p, int resident) {
+int persistent_groups(const LaunchParams &p, const LaunchHost &h, int resident) {
 #if defined(RT_STATS) || defined(RT_CYCLES)
     return 0;  // (these instrumented builds' probes live in the tiled prologue)
 #endif
     // a plain batch of one scene in its scene's shape, views and records in
     // device memory, counters to queue on
-    if (p.persistent0 <= 0 || (launch_shape(p, 0) & kLaunchPlain) == 0 || scene_shape(p, 0) == 0) return 0;
+    if (h.persistent0 <= 0 || (launch_shape(p, h, 0) & kLaunchPlain) == 0 || scene_shape(p.layout, h, 0) == 0) return 0;
     if (!p.views_dev || !p.consts_dev || p.n_views <= kMaxViews || !p.sched) return 0;
-    const bool forced = p.persistent0 >= 8;
-    const int groups = forced && p.persistent0 < resident ? p.persistent0 : resident;
+    const bool forced = h.persistent0 >= 8;
+    const int groups = forced && h.persistent0 < resident ? h.persistent0 : resident;
     const long long waves = static_cast<long long>(groups) * (kThreads / 64);
     const long long tiles = static_cast<long long>((p.width + 7) / 8) * ((p.height + 7) / 8) * p.n_views;
     if (waves < kQueues || tiles >= (1ll << 30)) return 0;  // (a queue without a wave; 32-bit item numbers)
@@ -2543,12 +2551,12 @@ int persistent_groups(const LaunchParams &p, int resident) {
     return groups;
 }
 
-int launch_shape(const LaunchParams &p, int max_depth, int resident) {
+int launch_shape(const LaunchParams &p, const LaunchHost &h, int max_depth, int resident) {
     if (resident > 0) {
-        const int shape = launch_shape(p, max_depth);
-        return shape | (shape != 0 && persistent_groups(p, resident) > 0 ? kLaunchPersistent : 0);
+        const int shape = launch_shape(p, h, max_depth);
+        return shape | (shape != 0 && persistent_groups(p, h, resident) > 0 ? kLaunchPersistent : 0);
     }
-    if (!p.shape_launch || max_depth != 0 || p.spp > 0) return 0;  // (RT_OPT_LAUNCH_SHAPES 0, deeper, Monte-Carlo)
+    if (!h.shape_launch || max_depth != 0 || p.spp > 0) return 0;  // (RT_OPT_LAUNCH_SHAPES 0, deeper, Monte-Carlo)
     const int slice_rows = p.slice_rows > 0 ? p.slice_rows : p.n_rows;  // (launch_render: 0 = the whole launch)
     const int slice_begin = p.slice_rows > 0 ? p.slice_begin : 0;
     const bool plain = p.n_shards <= 0 && p.row_begin == 0 && p.n_rows == p.height && slice_begin == 0 &&
@@ -2557,13 +2565,13 @@ int launch_shape(const LaunchParams &p, int max_depth, int resident) {
     return plain ? kLaunchPlain : 0;
 }
 
-size_t lds_bytes(const LaunchParams &p) {
+size_t lds_bytes(const SceneLayout &L, bool lean) {
     // blob + one view's records: per-sphere camera terms (16 B; not with
     // lean views) and footprint (16 B) + per-box camera terms
-    return (static_cast<size_t>(p.blob_units) + view_units(p)) * sizeof(float4);
+    return (static_cast<size_t>(L.blob_units) + view_units(L, lean)) * sizeof(float4);
 }
 
-int queued_views(const LaunchParams &p, int max_depth) {
+int queued_views(const SceneLayout &L, int max_depth) {
     const void *fn = nullptr;
     switch (max_depth) {  // (the view-batch kernels: no accumulation)
         case 2: fn = reinterpret_cast<const void *>(&render_kernel<2, false>); break;
@@ -2577,25 +2585,25 @@ int queued_views(const LaunchParams &p, int max_depth) {
         default: return 1;
     }
     static_assert(!kQueuedDepth(1) && kQueuedDepth(2), "queued from depth 2");
-    return queued_views_for(fn, p);
+    return queued_views_for(fn, L, false);  // (the general kernels: full view records)
 }
 
-hipError_t launch_render(LaunchParams &p, int max_depth, hipStream_t stream) {
+hipError_t launch_render(LaunchParams &p, const LaunchHost &h, int max_depth, hipStream_t stream) {
     if (p.slice_rows <= 0) {  // the whole launch as one slice
         p.slice_begin = 0;
         p.slice_rows = p.n_rows;
     }
     switch (max_depth) {
-        case 0: return launch_depth<0>(p, stream);
-        case 1: return launch_depth<1>(p, stream);
-        case 2: return launch_depth<2>(p, stream);
-        case 3: return launch_depth<3>(p, stream);
-        case 4: return launch_depth<4>(p, stream);
-        case 5: return launch_depth<5>(p, stream);
-        case 6: return launch_depth<6>(p, stream);
-        case 7: return launch_depth<7>(p, stream);
-        case 8: return launch_depth<8>(p, stream);
-        case 9: return launch_depth<9>(p, stream);
+        case 0: return launch_depth<0>(p, h, stream);
+        case 1: return launch_depth<1>(p, h, stream);
+        case 2: return launch_depth<2>(p, h, stream);
+        case 3: return launch_depth<3>(p, h, stream);
+        case 4: return launch_depth<4>(p, h, stream);
+        case 5: return launch_depth<5>(p, h, stream);
+        case 6: return launch_depth<6>(p, h, stream);
+        case 7: return launch_depth<7>(p, h, stream);
+        case 8: return launch_depth<8>(p, h, stream);
+        case 9: return launch_depth<9>(p, h, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -229,15 +229,15 @@ int rt_render_multi_view(rt_multi *m, const rt_scene *const *scenes, const rt_vi
         }
         if (rows[i] == 0) c->timed = false;  // no kernel of this device in this frame
         if (rows[i] > 0) {
-            LaunchParams p = base_params(c, scenes[i], view, 1, width, height);
+            LaunchHost h;
+            LaunchParams p = base_params(c, scenes[i], view, 1, width, height, h);
             p.row_begin = 0;
             p.n_rows = rows[i];
             p.block_rows = block_rows;
             p.n_shards = n;
             p.shard = i;
             p.out = static_cast<float4 *>(dst);
-            if ((rc = launch(c, p, max_depth, c->stream)) != RT_OK) return rc;
-            if ((rc = note_scene_use(scenes[i], c->stream)) != RT_OK) return rc;
+            if ((rc = launch_scene(c, scenes[i], p, h, max_depth, c->stream)) != RT_OK) return rc;
         }
         if ((e = hipEventRecord(m->rendered[i], c->stream)) != hipSuccess) return hip_fail("hipEventRecord", e);
     }

@@ -614,7 +614,7 @@ static void view_frame_setup(const LaunchParams &p, const FrameView &V, const fl
 
 void host_frame_setup(LaunchParams &p, const float4 *const *blobs) {
     p.n_frame_consts = 0;
-    const int ns = p.n_spheres, nb = p.n_boxes, per = 2 * ns + nb;
+    const int per = view_units(p.layout, false);
     if (per == 0 || per > kMaxViewConsts || p.n_views < 1 || p.n_views * per > kMaxFrameConsts) return;
     for (int k = 0; k < p.n_views; ++k)
         if (!blobs[k]) return;
@@ -623,7 +623,7 @@ void host_frame_setup(LaunchParams &p, const float4 *const *blobs) {
 }
 
 int host_view_consts(const LaunchParams &p, const FrameView &V, const float4 *blob, float4 *out) {
-    const int per = 2 * p.n_spheres + p.n_boxes;
+    const int per = view_units(p.layout, false);
     if (per == 0 || per > kMaxViewConsts || !blob) return 0;
     view_frame_setup(p, V, blob, out);
     return per;
@@ -631,14 +631,15 @@ int host_view_consts(const LaunchParams &p, const FrameView &V, const float4 *bl
 
 // One view's records (host_frame_setup).
 static void view_frame_setup(const LaunchParams &p, const FrameView &V, const float4 *blob, float4 *out) {
-    const int ns = p.n_spheres, nb = p.n_boxes;
+    const SceneLayout &L = p.layout;
+    const int ns = L.n_spheres, nb = L.n_boxes;
     const float ox = V.origin[0], oy = V.origin[1], oz = V.origin[2];
     const int hw = p.width / 2, hh = p.height / 2;
     const bool cull = V.cull && hw > 0 && hh > 0;
     const float *P = V.proj;
-    const auto *sph = reinterpret_cast<const SphereRec *>(blob + p.off_spheres);
-    const auto *meta = reinterpret_cast<const SphereMeta *>(blob + p.off_smeta);
-    const auto *box = reinterpret_cast<const BoxRec *>(blob + p.off_boxes);
+    const auto *sph = reinterpret_cast<const SphereRec *>(blob + L.off_spheres);
+    const auto *meta = reinterpret_cast<const SphereMeta *>(blob + L.off_smeta);
+    const auto *box = reinterpret_cast<const BoxRec *>(blob + L.off_boxes);
     float4 *cam = out, *px = out + ns, *bcam = out + 2 * ns;
     for (int s = 0; s < ns; ++s) {
         const SphereRec c = sph[s];
@@ -1043,17 +1044,17 @@ static void build_origin_lists(const std::vector<SphereRec> &sph, const std::vec
 int build_origin_lists_for(const std::vector<float4> &host, const DeviceScene &ds, std::vector<uint8_t> &olist) {
     olist.clear();
     if (!ds.olist_eligible) return RT_OK;
-    const size_t ns = static_cast<size_t>(ds.n_spheres);
-    if (host.size() * sizeof(float4) < (static_cast<size_t>(ds.off_smeta) * 16 + ns * sizeof(SphereMeta)) ||
-        host.size() * sizeof(float4) < (static_cast<size_t>(ds.off_spheres) * 16 + ns * sizeof(SphereRec))) {
+    const size_t ns = static_cast<size_t>(ds.layout.n_spheres);
+    if (host.size() * sizeof(float4) < (static_cast<size_t>(ds.layout.off_smeta) * 16 + ns * sizeof(SphereMeta)) ||
+        host.size() * sizeof(float4) < (static_cast<size_t>(ds.layout.off_spheres) * 16 + ns * sizeof(SphereRec))) {
         set_error("origin lists: the scene's host copy is incomplete");
         return RT_ERR_INVALID;
     }
     std::vector<SphereRec> sph(ns);
     std::vector<SphereMeta> smeta(ns);
     const char *base = reinterpret_cast<const char *>(host.data());
-    std::memcpy(sph.data(), base + static_cast<size_t>(ds.off_spheres) * 16, ns * sizeof(SphereRec));
-    std::memcpy(smeta.data(), base + static_cast<size_t>(ds.off_smeta) * 16, ns * sizeof(SphereMeta));
+    std::memcpy(sph.data(), base + static_cast<size_t>(ds.layout.off_spheres) * 16, ns * sizeof(SphereRec));
+    std::memcpy(smeta.data(), base + static_cast<size_t>(ds.layout.off_smeta) * 16, ns * sizeof(SphereMeta));
     try {
         build_origin_lists(sph, smeta, kOListTexels, olist);
     } catch (const std::bad_alloc &) {
@@ -1091,6 +1092,7 @@ MaskConeTable mask_cone_table(int n) {
 int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int n_mats, const rt_light *lights,
                 int n_lights, std::vector<float4> &blob, DeviceScene &ds, bool with_origin_lists,
                 double extent_floor) {
+    SceneLayout &lay = ds.layout;
     std::vector<SphereRec> sph;
     std::vector<SphereMeta> smeta;
     std::vector<BoxRec> boxes;
@@ -1231,12 +1233,12 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     }
     auto units = [](size_t bytes) { return static_cast<int32_t>((bytes + 15) / 16); };
     int32_t off = 0;
-    ds.off_spheres = off; off += units(sph.size() * sizeof(SphereRec));
-    ds.off_smeta = off;   off += units(smeta.size() * sizeof(SphereMeta));
-    ds.off_boxes = off;   off += units(boxes.size() * sizeof(BoxRec));
-    ds.off_mats = off;    off += units(mrec.size() * sizeof(MatRec));
-    ds.off_lights = off;  off += units(lrec.size() * sizeof(LightRec));
-    ds.off_lightmat = off; off += units(lm.size() * sizeof(LightMatRec));
+    lay.off_spheres = off; off += units(sph.size() * sizeof(SphereRec));
+    lay.off_smeta = off;   off += units(smeta.size() * sizeof(SphereMeta));
+    lay.off_boxes = off;   off += units(boxes.size() * sizeof(BoxRec));
+    lay.off_mats = off;    off += units(mrec.size() * sizeof(MatRec));
+    lay.off_lights = off;  off += units(lrec.size() * sizeof(LightRec));
+    lay.off_lightmat = off; off += units(lm.size() * sizeof(LightMatRec));
     // Round 6: in a scene of several boxes (chosen by the object kinds alone,
     // as the mask bits), per (box, light) the face plane of the box (in the
     // float32 transform the kernel uses) with the light farthest beyond it:
@@ -1249,7 +1251,7 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     // kept only if the light lies beyond by more than 0.01 (the segment ends
     // at L + 0.01 n, :808-809) + 2 m; else w = -inf (never beyond).
     std::vector<float4> bplane;
-    ds.off_bplane = -1;
+    lay.off_bplane = -1;
     if (boxes.size() >= 2) {
         bool finite = true;  // (a non-finite object: no planes; shaded points are bounded by `extent` otherwise)
         for (int i = 0; i < n_objs; ++i)
@@ -1279,11 +1281,11 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
                                                       static_cast<float>(bn[2]), static_cast<float>(bw - bm)};
             }
         }
-        ds.off_bplane = off;
+        lay.off_bplane = off;
         off += units(bplane.size() * sizeof(float4));
     }
-    ds.off_bvh = off;     off += units(bvh.size() * sizeof(BvhNode));
-    ds.off_blink = off;   off += units(blink.size() * sizeof(uint32_t));
+    lay.off_bvh = off;     off += units(bvh.size() * sizeof(BvhNode));
+    lay.off_blink = off;   off += units(blink.size() * sizeof(uint32_t));
     // The cone table rides in LDS only while the work-group's LDS stays small
     // enough for full occupancy (config 4's 256 spheres x 3 lights would add
     // 24 KB and cut the resident work-groups per CU); without it the kernel
@@ -1293,8 +1295,8 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     int n_live = 0;
     for (int j = 0; j < n_lights; ++j) n_live += lrec[j].dead == 0.0f;
     std::vector<uint64_t> dmask;
-    ds.off_dmask = -1;
-    ds.dmask_n = 0;
+    lay.off_dmask = -1;
+    lay.dmask_n = 0;
     // Round 6: in a scene of several boxes the boxes get mask bits too (bit
     // n_spheres + b), from their bounding spheres. A box that can occlude a
     // shadow segment holds a point of it, and so does its bounding sphere: the
@@ -1306,23 +1308,24 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     // scene — the room of configs 2-5 — keeps its box's shortcuts instead.
     const bool box_bits = boxes.size() >= 2;
     const size_t mask_bits = sph.size() + (box_bits ? boxes.size() : 0);
-    ds.dmask_box = 0;
+    lay.dmask_box = 0;
+    lay.dmask_bytes = 4;  // (without masks)
     if (!sph.empty() && mask_bits <= static_cast<size_t>(kMaskMaxSpheres) && n_live > 0) {
-        ds.dmask_bytes = mask_bits <= 16 ? 2 : (mask_bits <= 32 ? 4 : 8);
+        lay.dmask_bytes = mask_bits <= 16 ? 2 : (mask_bits <= 32 ? 4 : 8);
 #ifndef RT_DMASK_MAXN
 #define RT_DMASK_MAXN 12
 #endif
         for (int n : {32, 24, 16, 12, 8}) {
             if (n > RT_DMASK_MAXN) continue;
-            const size_t bytes = static_cast<size_t>(n_live) * 6 * n * n * ds.dmask_bytes;
+            const size_t bytes = static_cast<size_t>(n_live) * 6 * n * n * lay.dmask_bytes;
             if ((static_cast<size_t>(off) + units(bytes)) * 16 + per_frame <= kMaskLdsBudget) {
-                ds.dmask_n = n;
+                lay.dmask_n = n;
                 break;
             }
         }
     }
     std::vector<char> dmask_bytes;
-    if (ds.dmask_n > 0) {
+    if (lay.dmask_n > 0) {
         if (box_bits) {
             std::vector<SphereRec> bsph(sph);
             std::vector<SphereMeta> bmeta(smeta);
@@ -1346,47 +1349,47 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
                 bmeta.push_back({i, o.material, std::isfinite(rad) ? static_cast<float>(rad * (1.0 + 1e-6))
                                                                    : HUGE_VALF, 0});
             }
-            build_direction_masks(bsph, bmeta, lights, lrec, ds.dmask_n, dmask);
-            ds.dmask_box = 1;
+            build_direction_masks(bsph, bmeta, lights, lrec, lay.dmask_n, dmask);
+            lay.dmask_box = 1;
         } else {
-            build_direction_masks(sph, smeta, lights, lrec, ds.dmask_n, dmask);
+            build_direction_masks(sph, smeta, lights, lrec, lay.dmask_n, dmask);
         }
-        ds.off_dmask = off;
-        dmask_bytes.resize(dmask.size() * ds.dmask_bytes);
+        lay.off_dmask = off;
+        dmask_bytes.resize(dmask.size() * lay.dmask_bytes);
         for (size_t i = 0; i < dmask.size(); ++i)  // little-endian: the low bytes of each mask
-            std::memcpy(dmask_bytes.data() + i * ds.dmask_bytes, &dmask[i], ds.dmask_bytes);
+            std::memcpy(dmask_bytes.data() + i * lay.dmask_bytes, &dmask[i], lay.dmask_bytes);
         off += units(dmask_bytes.size());
         cones.clear();
     }
     const size_t with_cones = (static_cast<size_t>(off) + units(cones.size() * sizeof(ShadowCone))) * 16 + per_frame;
-    if (ds.dmask_n == 0 && with_cones <= kConeLdsBudget) {
-        ds.off_cone = off;
+    if (lay.dmask_n == 0 && with_cones <= kConeLdsBudget) {
+        lay.off_cone = off;
         off += units(cones.size() * sizeof(ShadowCone));
     } else {
-        ds.off_cone = -1;
+        lay.off_cone = -1;
         cones.clear();
     }
-    ds.n_bvh = static_cast<int32_t>(bvh.size());
-    ds.blob_units = off;  // the part every work-group stages into LDS
+    lay.n_bvh = static_cast<int32_t>(bvh.size());
+    lay.blob_units = off;  // the part every work-group stages into LDS
     // Scenes above RT_GMASK_FROM spheres: wide direction masks (kGMaskMaxSpheres),
     // also beside the LDS masks (depth 0-1 keep those; depth >= 2 reads these),
     // kept in the device blob past the staged part and read through L2.
     std::vector<uint64_t> gmask;
     std::vector<uint8_t> glist;
-    ds.off_gmask = -1;
-    ds.off_glist = -1;
-    ds.gmask_words = 0;
+    lay.off_gmask = -1;
+    lay.off_glist = -1;
+    lay.gmask_words = 0;
 #ifndef RT_GMASK_FROM
 #define RT_GMASK_FROM 32  // wide masks above this many spheres at depth >= 2 (tools/ablate.sh flags; config 3, 64 spheres: 1.15 -> 1.11 ms)
 #endif
     if (sph.size() > static_cast<size_t>(RT_GMASK_FROM) &&
         sph.size() <= static_cast<size_t>(kGMaskMaxSpheres) && n_live > 0) {
-        ds.gmask_words = static_cast<int32_t>((sph.size() + 63) / 64);
-        build_direction_masks(sph, smeta, lights, lrec, kGMaskTexels, gmask, ds.gmask_words);
-        ds.off_gmask = off;
+        lay.gmask_words = static_cast<int32_t>((sph.size() + 63) / 64);
+        build_direction_masks(sph, smeta, lights, lrec, kGMaskTexels, gmask, lay.gmask_words);
+        lay.off_gmask = off;
         off += units(gmask.size() * 8);
         // the candidate lists of the same texels (rt_internal.h kGListMax)
-        const size_t n_texels = gmask.size() / static_cast<size_t>(ds.gmask_words);
+        const size_t n_texels = gmask.size() / static_cast<size_t>(lay.gmask_words);
         glist.assign(n_texels * 16, 0);
         // each live light's order of the spheres: largest angular size seen
         // from the light first (a light inside a sphere's inflated bound, or
@@ -1422,8 +1425,8 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
             // the same truncation as the kernel's word walk (occluded: the
             // last word masked to the `rest` = ns - 64 w live slots)
             const int ns = static_cast<int>(sph.size());
-            for (int w = 0; w < ds.gmask_words; ++w) {
-                uint64_t bits = gmask[t * ds.gmask_words + w];
+            for (int w = 0; w < lay.gmask_words; ++w) {
+                uint64_t bits = gmask[t * lay.gmask_words + w];
                 const int rest = ns - 64 * w;
                 if (rest < 64) bits &= (uint64_t{1} << rest) - 1u;
                 for (; bits; bits &= bits - 1) {
@@ -1435,7 +1438,7 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
             if (n <= kGListMax)
                 std::sort(rec + 1, rec + 1 + n, [&](uint8_t x, uint8_t y) { return rk[x] < rk[y]; });
         }
-        ds.off_glist = off;
+        lay.off_glist = off;
         off += units(glist.size());
     }
     // The secondary rays' origin-sphere candidate lists (rt_internal.h
@@ -1447,38 +1450,38 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     // with_origin_lists: built here, at the blob's end (the CPU models'
     // rt_debug_scene_blob).
     std::vector<uint8_t> olist;
-    ds.off_olist = -1;
+    lay.off_olist = -1;
     ds.olist_eligible = sph.size() >= static_cast<size_t>(kOListMinSpheres) && sph.size() <= 256;
     if (ds.olist_eligible && with_origin_lists) {
         build_origin_lists(sph, smeta, kOListTexels, olist);
-        ds.off_olist = off;
+        lay.off_olist = off;
         off += units(olist.size());
     }
-    ds.n_spheres = static_cast<int32_t>(sph.size());
-    ds.n_boxes = static_cast<int32_t>(boxes.size());
+    lay.n_spheres = static_cast<int32_t>(sph.size());
+    lay.n_boxes = static_cast<int32_t>(boxes.size());
     ds.room = boxes.size() == 1 && boxes[0].translate_only;
     for (int j = 0; j < n_lights && ds.room; ++j)
         if (lrec[j].dead == 0.0f && (j >= 32 || !((boxes[0].light_inside >> j) & 1u))) ds.room = 0;
-    ds.n_mats = n_mats;
-    ds.n_lights = n_lights;
+    lay.n_mats = n_mats;
+    lay.n_lights = n_lights;
     blob.assign(static_cast<size_t>(off > 0 ? off : 1), float4{0, 0, 0, 0});
     auto put = [&](int32_t at, const void *src, size_t bytes) {
         if (bytes) std::memcpy(reinterpret_cast<char *>(blob.data()) + static_cast<size_t>(at) * 16, src, bytes);
     };
-    put(ds.off_spheres, sph.data(), sph.size() * sizeof(SphereRec));
-    put(ds.off_smeta, smeta.data(), smeta.size() * sizeof(SphereMeta));
-    put(ds.off_boxes, boxes.data(), boxes.size() * sizeof(BoxRec));
-    put(ds.off_mats, mrec.data(), mrec.size() * sizeof(MatRec));
-    put(ds.off_lights, lrec.data(), lrec.size() * sizeof(LightRec));
-    put(ds.off_lightmat, lm.data(), lm.size() * sizeof(LightMatRec));
-    if (ds.off_bplane >= 0) put(ds.off_bplane, bplane.data(), bplane.size() * sizeof(float4));
-    put(ds.off_bvh, bvh.data(), bvh.size() * sizeof(BvhNode));
-    put(ds.off_blink, blink.data(), blink.size() * sizeof(uint32_t));
-    if (ds.off_cone >= 0) put(ds.off_cone, cones.data(), cones.size() * sizeof(ShadowCone));
-    if (ds.off_dmask >= 0) put(ds.off_dmask, dmask_bytes.data(), dmask_bytes.size());
-    if (ds.off_gmask >= 0) put(ds.off_gmask, gmask.data(), gmask.size() * 8);
-    if (ds.off_glist >= 0) put(ds.off_glist, glist.data(), glist.size());
-    if (ds.off_olist >= 0) put(ds.off_olist, olist.data(), olist.size());
+    put(lay.off_spheres, sph.data(), sph.size() * sizeof(SphereRec));
+    put(lay.off_smeta, smeta.data(), smeta.size() * sizeof(SphereMeta));
+    put(lay.off_boxes, boxes.data(), boxes.size() * sizeof(BoxRec));
+    put(lay.off_mats, mrec.data(), mrec.size() * sizeof(MatRec));
+    put(lay.off_lights, lrec.data(), lrec.size() * sizeof(LightRec));
+    put(lay.off_lightmat, lm.data(), lm.size() * sizeof(LightMatRec));
+    if (lay.off_bplane >= 0) put(lay.off_bplane, bplane.data(), bplane.size() * sizeof(float4));
+    put(lay.off_bvh, bvh.data(), bvh.size() * sizeof(BvhNode));
+    put(lay.off_blink, blink.data(), blink.size() * sizeof(uint32_t));
+    if (lay.off_cone >= 0) put(lay.off_cone, cones.data(), cones.size() * sizeof(ShadowCone));
+    if (lay.off_dmask >= 0) put(lay.off_dmask, dmask_bytes.data(), dmask_bytes.size());
+    if (lay.off_gmask >= 0) put(lay.off_gmask, gmask.data(), gmask.size() * 8);
+    if (lay.off_glist >= 0) put(lay.off_glist, glist.data(), glist.size());
+    if (lay.off_olist >= 0) put(lay.off_olist, olist.data(), olist.size());
     return RT_OK;
 }
 

@@ -52,11 +52,7 @@ void parse_and_build(const std::string &text, float t) {
         p.view[0].cull = 1;
         p.width = 320;
         p.height = 180;
-        p.n_spheres = ds.n_spheres;
-        p.n_boxes = ds.n_boxes;
-        p.off_spheres = ds.off_spheres;
-        p.off_smeta = ds.off_smeta;
-        p.off_boxes = ds.off_boxes;
+        p.layout = ds.layout;
         const float4 *blobs[1] = {blob.data()};
         rtamd::host_frame_setup(p, blobs);
     }

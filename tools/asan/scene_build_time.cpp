@@ -43,9 +43,9 @@ int main() {
         std::vector<float4> blob;
         rtamd::DeviceScene ds;
         rtamd::build_scene(objs.data(), n + 1, mats, RT_REFERENCE_MATERIALS, lights, RT_REFERENCE_LIGHTS, blob, ds, false);
-        if (ds.off_glist >= 0) {  // candidate-list lengths of the wide masks (rt_internal.h kGListMax)
-            const unsigned char *g = reinterpret_cast<const unsigned char *>(blob.data()) + 16L * ds.off_glist;
-            const long texels = (static_cast<long>(blob.size()) - ds.off_glist);
+        if (ds.layout.off_glist >= 0) {  // candidate-list lengths of the wide masks (rt_internal.h kGListMax)
+            const unsigned char *g = reinterpret_cast<const unsigned char *>(blob.data()) + 16L * ds.layout.off_glist;
+            const long texels = (static_cast<long>(blob.size()) - ds.layout.off_glist);
             long over = 0, hist[4] = {0, 0, 0, 0};
             double sum = 0;
             for (long t = 0; t < texels; ++t) {
@@ -58,10 +58,10 @@ int main() {
                         "overflow (> 15): %ld\n", n, texels, sum / (texels - over), hist[0], hist[1], hist[2], hist[3], over);
         }
         // LDS per work-group: the staged blob + per-sphere camera terms and footprints + per-box camera terms
-        const long lds = 16L * (ds.blob_units + 2L * n + 1);
+        const long lds = 16L * (ds.layout.blob_units + 2L * n + 1);
         std::printf("room + %3d spheres: scene build %.3f ms (median of 7), blob %016llx, LDS %ld B (masks %d B)\n", n,
                     ms[3], static_cast<unsigned long long>(hash), lds,
-                    ds.off_dmask >= 0 ? 16 * (ds.blob_units - ds.off_dmask) : 0);
+                    ds.layout.off_dmask >= 0 ? 16 * (ds.layout.blob_units - ds.layout.off_dmask) : 0);
         if (ds.olist_eligible) {  // the origin-sphere lists, built on a scene's first deep render
             std::vector<double> ol;
             std::vector<uint8_t> olist;
