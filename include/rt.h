@@ -172,6 +172,17 @@ int rt_reference_animation(rt_object base[RT_REFERENCE_OBJECTS], rt_object_anim 
  * objects, so a scale channel that passes through 0 does not turn a box into
  * a sphere there (rt_scene_create of this function's output would). */
 int rt_animate_objects(const rt_object *base, const rt_object_anim *anim, int n_objs, float time, rt_object *out);
+/* The same with a radius channel per object beside the description (a sphere
+ * has one field rt_object_anim cannot express): radius[i], n_objs entries in
+ * the five forms above, replaces out[i].radius. radius == NULL: no radius
+ * moves, and the result equals rt_animate_objects byte for byte. The kind rule
+ * above holds for the radius too: on the animated entry points a radius
+ * channel that passes through -1 does not turn a sphere into a null object
+ * (there it is a sphere of radius 1, as any negative radius r other than -1
+ * is a sphere of radius |r|); rt_scene_create of this function's output would
+ * make that change. */
+int rt_animate_objects2(const rt_object *base, const rt_object_anim *anim, const rt_anim_channel *radius, int n_objs,
+                        float time, rt_object *out);
 
 /* The transforms a box object is intersected with, as the reference's GL
  * evaluates them per ray (raytrace_compute.glsl:650-652, :718, replacing
@@ -298,19 +309,36 @@ int rt_render_batch_scenes(rt_context *ctx, const rt_scene *const *scenes, const
  * An animated scene: the base objects and their channels, resident on the
  * device. A render at `time` runs an animate kernel on the call's stream
  * that evaluates the channels and rewrites the time-dependent parts of the
- * scene (the boxes' transforms and their culling data), then the existing
+ * scene (the boxes' transforms and their culling data; with rt_anim_create2
+ * the moving spheres and theirs), then the existing
  * render: no host rebuild, no upload and no host synchronisation per frame
  * (the reference: one uniform, raytrace_compute.glsl:236-237, main.cpp:226).
- * The frame is bit-identical to rt_scene_update(rt_animate_objects(time))
- * followed by the corresponding existing render call.
+ * The frame is bit-identical to rt_scene_update(rt_animate_objects(time)) —
+ * rt_animate_objects2 with radius channels — followed by the corresponding
+ * existing render call.
  *
- * Channels are supported on box objects only: an animated sphere (or null
- * object) is refused with RT_ERR_UNSUPPORTED (moving spheres would need the
- * sphere BVH, the cones and the candidate lists rebuilt on the device).
- * Spheres may be present and static. A scene with a RATE / RATE_OFFSET
- * channel on a position or on the scale is laid out for |time| <= 1e4 (its
- * culling margins grow with the farthest the boxes can get); a render outside
- * that range returns RT_ERR_UNSUPPORTED. `time` must also respect the sin /
+ * rt_anim_create supports channels on box objects only: an animated sphere
+ * (or null object) is refused with RT_ERR_UNSUPPORTED. Spheres may be present
+ * and static, in any number.
+ * rt_anim_create2 takes a radius channel per object as well (radius, n_objs
+ * entries or NULL, as rt_animate_objects2) and moves spheres too: a sphere is
+ * moving when a position channel or its radius channel is not RT_ANIM_NONE.
+ * The animate kernel then also rewrites the moving spheres' records, refits
+ * the bounds of the sphere BVH (its topology is built once, from the base
+ * objects), and rewrites their shadow cones and their bits in the shadow
+ * direction masks. Angle and scale channels on a sphere are accepted and
+ * evaluated by rt_animate_objects2; the render never reads them. An object's
+ * kind is its base's (see rt_animate_objects2). Limits: a scene with a moving
+ * sphere holds at most 32 spheres in all (larger scenes carry wide masks,
+ * candidate lists and origin-sphere lists, which are not rebuilt on the
+ * device): RT_ERR_UNSUPPORTED otherwise; a moving sphere's base position and
+ * radius and its channels' a, k, c must be finite (RT_ERR_INVALID); channels
+ * on null objects stay refused. With radius == NULL and no channel on a
+ * sphere it behaves as rt_anim_create.
+ * A scene with a RATE / RATE_OFFSET channel on a position, on the scale or on
+ * a radius is laid out for |time| <= 1e4 (its culling margins grow with the
+ * farthest the objects can get); a render outside that range returns
+ * RT_ERR_UNSUPPORTED. `time` must also respect the sin /
  * cos range above. A scene of 33-256 spheres gets its origin-sphere lists at
  * creation, in each of the max_frames frame slots.
  *
@@ -327,6 +355,9 @@ typedef struct rt_anim rt_anim;
 int rt_anim_create(rt_context *ctx, const rt_object *base, const rt_object_anim *anim, int n_objs,
                    const rt_material *mats, int n_mats, const rt_light *lights, int n_lights, int max_frames,
                    rt_anim **out);
+int rt_anim_create2(rt_context *ctx, const rt_object *base, const rt_object_anim *anim, const rt_anim_channel *radius,
+                    int n_objs, const rt_material *mats, int n_mats, const rt_light *lights, int n_lights,
+                    int max_frames, rt_anim **out);
 void rt_anim_destroy(rt_anim *anim);
 /* rt_render with the objects at `time` too: cam NULL = the orbit camera at `time`. */
 int rt_render_animated(rt_context *ctx, rt_anim *anim, const rt_camera *cam, float time, int width, int height,

@@ -84,6 +84,10 @@ def lib():
             "rt_render_animated": ([vp, vp, vp, f, i, i, i, i, i, vp, i, vp], i),
             "rt_render_batch_animated": ([vp, vp, vp, vp, i, i, i, i, i, i, i, vp, vp], i),
             "rt_debug_anim_blob": ([vp, f, vp, C.c_longlong], C.c_longlong),
+            "rt_animate_objects2": ([vp, vp, vp, i, f, vp], i),
+            "rt_anim_create2": ([vp, vp, vp, vp, i, vp, i, vp, i, i, vp], i),
+            "rt_debug_anim_validate": ([vp, vp, vp, i, vp, i, vp, i, i, i], i),
+            "rt_debug_anim_host_blob": ([vp, vp, vp, i, vp, i, vp, i, f, vp, C.c_longlong, vp], C.c_longlong),
         }
         for name, (args, res) in sig.items():
             fn = getattr(L, name)
@@ -131,14 +135,58 @@ def reference_animation():
     return list(base), list(anim)
 
 
-def animate_objects(base, anim, time):
-    """rt_animate_objects: the objects at `time` (host, float32 as written)."""
+def animate_objects(base, anim, time, radius=None):
+    """rt_animate_objects: the objects at `time` (host, float32 as written);
+    with `radius` (an AnimChannel per object), rt_animate_objects2."""
     n = len(base)
     b = (Object * max(n, 1))(*base)
     a = (abi.ObjectAnim * max(n, 1))(*anim)
     out = (Object * max(n, 1))()
-    _check(lib().rt_animate_objects(b, a, n, time, out))
+    if radius is None:
+        _check(lib().rt_animate_objects(b, a, n, time, out))
+    else:
+        r = (abi.AnimChannel * max(n, 1))(*radius)
+        _check(lib().rt_animate_objects2(b, a, r, n, time, out))
     return list(out[:n])
+
+
+def _is_box(o):
+    return any(x != 0.0 for x in list(o.box_mins) + list(o.box_maxs))
+
+
+def _anim_args(base, anim, radius, materials, lights):
+    materials = materials if materials is not None else reference_materials()
+    lights = lights if lights is not None else reference_lights()
+    objs = (Object * max(len(base), 1))(*base)
+    an = (abi.ObjectAnim * max(len(anim), 1))(*anim)
+    rad = (abi.AnimChannel * max(len(base), 1))(*radius) if radius is not None else None
+    mats = (Material * len(materials))(*materials)
+    lts = (Light * max(len(lights), 1))(*lights)
+    return objs, an, rad, len(base), mats, len(materials), lts, len(lights)
+
+
+def anim_validate(base, anim, radius=None, materials=None, lights=None, max_frames=1, boxes_only=False):
+    """rt_debug_anim_validate (host only): the (code, message) rt_anim_create2
+    — rt_anim_create with boxes_only — would return for this description."""
+    rc = lib().rt_debug_anim_validate(*_anim_args(base, anim, radius, materials, lights), max_frames,
+                                      1 if boxes_only else 0)
+    return rc, (lib().rt_last_error().decode() if rc != RT_OK else "")
+
+
+def anim_host_blob(base, anim, radius=None, materials=None, lights=None, time=0.0):
+    """rt_debug_anim_host_blob (host only): (the slot blob at `time` as the
+    host makes it with the animate kernel's functions, rt_debug_scene_blob's
+    24 meta ints)."""
+    args = _anim_args(base, anim, radius, materials, lights)
+    meta = (C.c_int32 * 24)()
+    n = lib().rt_debug_anim_host_blob(*args, time, None, 0, meta)
+    if n < 0:
+        raise RTError(int(n), lib().rt_last_error().decode())
+    buf = np.zeros(int(n), np.uint8)
+    n = lib().rt_debug_anim_host_blob(*args, time, buf.ctypes.data, buf.size, meta)
+    if n < 0:
+        raise RTError(int(n), lib().rt_last_error().decode())
+    return buf, list(meta)
 
 
 def bench_objects(n_spheres, seed=0):
@@ -330,19 +378,21 @@ class Scene:
 
 class Anim:
     """Device-resident animated scene (rt_anim_create): base objects and their
-    channels; `max_frames` frames may be in flight at once. Defaults: the
-    reference's 7 materials and 3 lights."""
+    channels; `max_frames` frames may be in flight at once. With `radius` (an
+    AnimChannel per object), or a channel on an object that is not a box,
+    rt_anim_create2: spheres move too. Defaults: the reference's 7 materials
+    and 3 lights."""
 
-    def __init__(self, ctx, base, anim, materials=None, lights=None, max_frames=1):
-        materials = materials if materials is not None else reference_materials()
-        lights = lights if lights is not None else reference_lights()
-        objs = (Object * max(len(base), 1))(*base)
-        an = (abi.ObjectAnim * max(len(anim), 1))(*anim)
-        mats = (Material * len(materials))(*materials)
-        lts = (Light * max(len(lights), 1))(*lights)
+    def __init__(self, ctx, base, anim, materials=None, lights=None, max_frames=1, radius=None):
+        objs, an, rad, n, mats, nm, lts, nl = _anim_args(base, anim, radius, materials, lights)
         self._h = C.c_void_p()
-        _check(lib().rt_anim_create(ctx.handle, objs, an, len(base), mats, len(materials), lts, len(lights),
-                                    max_frames, C.byref(self._h)))
+        moving = [any(c.kind != abi.RT_ANIM_NONE for c in [a.scale] + list(a.position) + list(a.angles))
+                  for a in anim]
+        if radius is not None or any(m and not _is_box(o) for m, o in zip(moving, base)):
+            _check(lib().rt_anim_create2(ctx.handle, objs, an, rad, n, mats, nm, lts, nl, max_frames,
+                                         C.byref(self._h)))
+        else:
+            _check(lib().rt_anim_create(ctx.handle, objs, an, n, mats, nm, lts, nl, max_frames, C.byref(self._h)))
         self.ctx = ctx
         self.max_frames = max_frames
 

@@ -15,6 +15,20 @@
 //      the LDS direction masks' box bits, every (box, live light) cone;
 //   3. the direction masks: one thread per texel ORs the boxes' bits into the
 //      static spheres' template mask.
+// Scenes with moving spheres (rt_anim_create2) run the kernel's second
+// instance, animate_kernel<true>, which adds in the same phases, with the
+// arithmetic of rt_anim.h (the text the host runs):
+//   1. one lane per moving sphere: its SphereRec and SphereMeta::radius; one
+//      lane per sphere slot, moving or not: its float64 box with build_bvh's
+//      margin, in LDS;
+//   2. one thread per BVH node: the node's six bounds, the union of the boxes
+//      of its subtree's range of sphere slots (the topology, skip links, leaf words
+//      and octant links stay the template's); per (moving sphere, light) the
+//      ShadowCone where the layout has that table; per (moving sphere, live
+//      light) the mask cone;
+//   3. the moving spheres' bits in the direction masks, also in scenes
+//      without box bits.
+// Box-only scenes keep animate_kernel<false>, whose code carries none of that.
 // The culling data (light_inside, planes, mask bits) use build_scene's
 // inequalities and margins in float64; they need not equal the host's bit for
 // bit (the device's double sin / cos may differ in the last place) and are as
@@ -32,14 +46,15 @@ namespace {
 
 constexpr int kAnimThreads = 256;
 
-struct BoxCone {  // a box's bounding sphere seen from a live light (build_direction_masks)
-    double ax[3], ch, sh, every;
-};
-
-// LDS: [flag, 16 B][n float4 bounding spheres][n x n_live BoxCone], n = the
-// boxes with mask bits
+// LDS: [flag, 16 B][n float4 balls][n x n_live MaskCone][n_spheres
+// AnimSphereBox, scenes with a moving sphere], n = the balls with mask bits
+// the kernel recomputes (anim_mask_balls: the boxes' bounding spheres, then
+// the moving spheres)
 __host__ __device__ inline size_t lds_spheres_at() { return 16; }
-__host__ __device__ inline size_t lds_cones_at(int n_mask_boxes) { return 16 + static_cast<size_t>(n_mask_boxes) * 16; }
+__host__ __device__ inline size_t lds_cones_at(int n_balls) { return 16 + static_cast<size_t>(n_balls) * 16; }
+__host__ __device__ inline size_t lds_boxes_at(int n_balls, int n_live) {
+    return lds_cones_at(n_balls) + static_cast<size_t>(n_balls) * n_live * sizeof(MaskCone);
+}
 
 // build_scene's float64 rotation of an object (culling only): Rz(yaw) Rx(pitch)
 // Ry(roll), each angle the float DEG_TO_RAD * deg; R[col][row].
@@ -66,6 +81,7 @@ __device__ void rotation64(const float ang[3], double R[3][3]) {
     mul(zx, y, R);
 }
 
+template <bool kSpheres>
 __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams p) {
     extern __shared__ double lds_raw[];
     unsigned char *lds = reinterpret_cast<unsigned char *>(lds_raw);
@@ -75,13 +91,19 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
     unsigned char *blob = p.blobs + static_cast<size_t>((p.first_slot + frame) % p.n_slots) * p.slot_bytes;
     const int nb = T.n_boxes, nl = T.n_lights;
     const int n_mask_boxes = T.dmask_box ? nb : 0;
+    const int n_ms = kSpheres ? T.n_msph : 0;
+    const int n_balls = n_mask_boxes + (kSpheres && T.dmask_n > 0 ? n_ms : 0);
     int *bad = reinterpret_cast<int *>(lds);  // 1: an animated field the plane test looks at is not finite
     float4 *bsph = reinterpret_cast<float4 *>(lds + lds_spheres_at());
-    BoxCone *cones = reinterpret_cast<BoxCone *>(lds + lds_cones_at(n_mask_boxes));
+    MaskCone *cones = reinterpret_cast<MaskCone *>(lds + lds_cones_at(n_balls));
+    AnimSphereBox *sbox = reinterpret_cast<AnimSphereBox *>(lds + lds_boxes_at(n_balls, T.n_live));
     const rt_object *base = reinterpret_cast<const rt_object *>(p.table + T.off_base);
     const rt_object_anim *anim = reinterpret_cast<const rt_object_anim *>(p.table + T.off_anim);
     const float4 *light = reinterpret_cast<const float4 *>(p.table + T.off_light);
     BoxRec *boxes = reinterpret_cast<BoxRec *>(blob + static_cast<size_t>(p.off_boxes) * 16);
+    const AnimSphere *msph = reinterpret_cast<const AnimSphere *>(p.table + T.off_msph);
+    SphereRec *sph = reinterpret_cast<SphereRec *>(blob + static_cast<size_t>(T.blob_spheres) * 16);
+    SphereMeta *smeta = reinterpret_cast<SphereMeta *>(blob + static_cast<size_t>(T.blob_smeta) * 16);
     if (tid == 0) *bad = 0;
     __syncthreads();
 
@@ -119,6 +141,11 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
             rec.translate_only = translate_only;
             if (!finite) *bad = 1;
         }
+        // the static spheres' boxes for the BVH refit, one lane per slot
+        // (the moving spheres' lanes store theirs below)
+        if (kSpheres && n_ms > 0)
+            for (int s = tid; s < T.n_spheres; s += kHalf)
+                if (!((T.moving_slots >> s) & 1u)) sbox[s] = anim_sphere_box(sph[s], smeta[s].radius, T.extent);
     } else {
         for (int b = tid - kHalf; b < nb; b += kHalf) {
             const rt_object o = animate_object(base[b], anim[b], time);
@@ -157,6 +184,17 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
                                       isfinite(rad) ? static_cast<float>(rad * (1.0 + 1e-6)) : HUGE_VALF);
             }
         }
+        if (kSpheres)
+            for (int i = tid - kHalf; i < n_ms; i += kHalf) {
+                const AnimSphere s = msph[i];
+                SphereRec rec;
+                float rad;
+                anim_sphere_records(s, time, rec, rad);
+                sph[s.slot] = rec;
+                smeta[s.slot].radius = rad;
+                sbox[s.slot] = anim_sphere_box(rec, rad, T.extent);
+                if (n_balls > n_mask_boxes) bsph[n_mask_boxes + i] = make_float4(rec.cx, rec.cy, rec.cz, rad);
+            }
     }
     __syncthreads();
 
@@ -191,27 +229,41 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
             bplane[i] = out;
         }
     }
-    for (int i = tid; i < n_mask_boxes * nl; i += kAnimThreads) {
+    for (int i = tid; i < n_balls * nl; i += kAnimThreads) {
         const int b = i / nl, j = i % nl;
         const float4 lj = light[j];
         const int li = __float_as_int(lj.w);
         if (li < 0) continue;  // a dead light has no mask
         const float4 s = bsph[b];
-        const double v[3] = {double(s.x) - double(lj.x), double(s.y) - double(lj.y), double(s.z) - double(lj.z)};
-        const double d = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        const double rp = double(s.w) + 0.021 + 1e-3 * d;
-        BoxCone c = {{0.0, 0.0, 0.0}, 0.0, 0.0, 0.0};
-        if (!(isfinite(d) && isfinite(rp)) || d <= rp) {
-            c.every = 1.0;
-        } else {
-            for (int k = 0; k < 3; ++k) c.ax[k] = v[k] / d;
-            const double half = asin(fmin(1.0, rp / d));
-            c.ch = cos(half + 1e-3);
-            c.sh = sin(half + 1e-3);
-        }
-        cones[b * T.n_live + li] = c;
+        const float ball[4] = {s.x, s.y, s.z, s.w}, lp[3] = {lj.x, lj.y, lj.z};
+        int bit = T.n_spheres + b;
+        if (kSpheres && b >= n_mask_boxes) bit = msph[b - n_mask_boxes].slot;
+        cones[b * T.n_live + li] = anim_mask_cone(ball, lp, bit);
     }
-    if (n_mask_boxes == 0) return;  // (uniform: every thread of the launch)
+    if (kSpheres && n_ms > 0) {
+        // the BVH's bounds, node by node, from the spheres' boxes
+        const AnimNodeRange *range = reinterpret_cast<const AnimNodeRange *>(p.table + T.off_node);
+        BvhNode *bvh = reinterpret_cast<BvhNode *>(blob + static_cast<size_t>(T.blob_bvh) * 16);
+        for (int n = tid; n < T.n_bvh; n += kAnimThreads) {
+            float lo[3], hi[3];
+            anim_node_bounds(sbox, range[n], lo, hi);
+            for (int a = 0; a < 3; ++a) {
+                bvh[n].lo[a] = lo[a];
+                bvh[n].hi[a] = hi[a];
+            }
+        }
+        if (T.blob_cone >= 0) {
+            // the ShadowCone table's entries of the moving spheres, every light's
+            ShadowCone *scone = reinterpret_cast<ShadowCone *>(blob + static_cast<size_t>(T.blob_cone) * 16);
+            for (int i = kAnimThreads - 1 - tid; i < n_ms * nl; i += kAnimThreads) {
+                const int slot = msph[i / nl].slot, j = i % nl;
+                const float4 lj = light[j];
+                const float lp[3] = {lj.x, lj.y, lj.z};
+                scone[j * T.n_spheres + slot] = anim_shadow_cone(sph[slot], smeta[slot].radius, lp);
+            }
+        }
+    }
+    if (n_balls == 0) return;  // (uniform: every thread of the launch)
     __syncthreads();
 
     // ---- 3. direction masks: the texel test, texel by texel --------------
@@ -222,14 +274,10 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
     for (int i = tid; i < T.n_live * texels; i += kAnimThreads) {
         const int li = i / texels, t = i % texels;
         const double *w = cone_tab + 5 * static_cast<size_t>(t);
-        const double ca = w[3], sa = w[4];
         uint64_t bits = 0;
-        for (int b = 0; b < n_mask_boxes; ++b) {
-            const BoxCone &c = cones[b * T.n_live + li];
-            // cos(alpha + half + 1e-3), less 1e-12 for rounding (build_direction_masks)
-            const double lim = ca * c.ch - sa * c.sh - 1e-12;
-            const double dot = w[0] * c.ax[0] + w[1] * c.ax[1] + w[2] * c.ax[2];
-            if (c.every != 0.0 || dot >= lim) bits |= uint64_t{1} << (T.n_spheres + b);
+        for (int b = 0; b < n_balls; ++b) {
+            const MaskCone &c = cones[b * T.n_live + li];
+            if (anim_texel_hit(w, c)) bits |= uint64_t{1} << c.bit;
         }
         if (T.dmask_bytes == 2)
             reinterpret_cast<uint16_t *>(dmask)[i] =
@@ -245,12 +293,15 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
 }  // namespace
 
 size_t animate_lds(const AnimTable &t) {
-    const int n = t.dmask_box ? t.n_boxes : 0;
-    return lds_cones_at(n) + static_cast<size_t>(n) * t.n_live * sizeof(BoxCone);
+    const int n = anim_mask_balls(t);
+    return lds_boxes_at(n, t.n_live) + (t.n_msph > 0 ? static_cast<size_t>(t.n_spheres) * sizeof(AnimSphereBox) : 0);
 }
 
-hipError_t launch_animate(const AnimParams &p, int n_frames, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL(animate_kernel, dim3(n_frames), dim3(kAnimThreads), lds, stream, p);
+hipError_t launch_animate(const AnimParams &p, bool spheres, int n_frames, size_t lds, hipStream_t stream) {
+    if (spheres)
+        hipLaunchKernelGGL(animate_kernel<true>, dim3(n_frames), dim3(kAnimThreads), lds, stream, p);
+    else
+        hipLaunchKernelGGL(animate_kernel<false>, dim3(n_frames), dim3(kAnimThreads), lds, stream, p);
     return hipGetLastError();
 }
 

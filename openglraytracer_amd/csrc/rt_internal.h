@@ -542,6 +542,7 @@ struct rt_context {
     hipEvent_t sched_done[rtamd::kSchedSlots] = {};
     bool sched_used[rtamd::kSchedSlots] = {};
     bool last_queued = false;   // the last launch used its slot (rt_debug_last_queued)
+    int last_shape = 0;         // the last launch's scene shape (rt_debug_last_scene_shape)
     std::vector<struct rt_scene *> scenes;  // live scenes (detached by rt_destroy)
 };
 

@@ -251,22 +251,40 @@ int rt_reference_animation(rt_object base[RT_REFERENCE_OBJECTS], rt_object_anim 
     return RT_OK;
 }
 
-int rt_animate_objects(const rt_object *base, const rt_object_anim *anim, int n_objs, float time, rt_object *out) {
+// rt_animate_objects (radius NULL) and rt_animate_objects2
+static int animate_objects(const char *who, const rt_object *base, const rt_object_anim *anim,
+                           const rt_anim_channel *radius, int n_objs, float time, rt_object *out) {
     if (n_objs < 0 || (n_objs > 0 && (!base || !anim || !out))) {
-        set_error("rt_animate_objects: null argument or negative count");
+        set_error(std::string(who) + ": null argument or negative count");
         return RT_ERR_INVALID;
     }
     for (int i = 0; i < n_objs; ++i) {
         const rt_anim_channel *c = &anim[i].scale;  // 7 channels, contiguous
-        for (int k = 0; k < 7; ++k)
-            if (c[k].kind < RT_ANIM_NONE || c[k].kind > RT_ANIM_SIN_OFFSET) {
-                set_error("rt_animate_objects: object " + std::to_string(i) + " has a channel of unknown kind " +
-                          std::to_string(c[k].kind));
+        for (int k = 0; k < 8; ++k) {
+            if (k == 7 && !radius) break;
+            const int kind = k < 7 ? c[k].kind : radius[i].kind;
+            if (kind < RT_ANIM_NONE || kind > RT_ANIM_SIN_OFFSET) {
+                set_error(std::string(who) + ": object " + std::to_string(i) + " has a channel of unknown kind " +
+                          std::to_string(kind));
                 return RT_ERR_INVALID;
             }
+        }
     }
-    for (int i = 0; i < n_objs; ++i) out[i] = animate_object(base[i], anim[i], time);
+    for (int i = 0; i < n_objs; ++i) {
+        const float r = radius ? anim_channel(radius[i], time, base[i].radius) : base[i].radius;
+        out[i] = animate_object(base[i], anim[i], time);
+        out[i].radius = r;
+    }
     return RT_OK;
+}
+
+int rt_animate_objects(const rt_object *base, const rt_object_anim *anim, int n_objs, float time, rt_object *out) {
+    return animate_objects("rt_animate_objects", base, anim, nullptr, n_objs, time, out);
+}
+
+int rt_animate_objects2(const rt_object *base, const rt_object_anim *anim, const rt_anim_channel *radius, int n_objs,
+                        float time, rt_object *out) {
+    return animate_objects("rt_animate_objects2", base, anim, radius, n_objs, time, out);
 }
 
 // raytrace_compute.glsl:334-364 (run-time sin / cos and mod() as the
@@ -1485,4 +1503,387 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     return RT_OK;
 }
 
+// ---- animated scenes: the host's side of rt_anim_create / rt_anim_create2 ----
+namespace {
+
+// largest |value| a channel takes over the supported times
+double channel_bound(const rt_anim_channel &ch, double base) {
+    const double T = kAnimTimeBound;
+    switch (ch.kind) {
+        case RT_ANIM_RATE: return std::fabs(double(ch.k)) * T;
+        case RT_ANIM_RATE_OFFSET: return std::fabs(double(ch.c)) + std::fabs(double(ch.k)) * T;
+        case RT_ANIM_SIN: return std::fabs(double(ch.a)) * 1.0001;  // (the polynomial sin stays within 1 + 2^-20)
+        case RT_ANIM_SIN_OFFSET: return std::fabs(double(ch.a)) * 1.0001 + std::fabs(double(ch.c));
+        default: return std::fabs(base);
+    }
+}
+bool channel_grows(const rt_anim_channel &ch) { return ch.kind == RT_ANIM_RATE || ch.kind == RT_ANIM_RATE_OFFSET; }
+bool channel_finite(const rt_anim_channel &ch) {
+    return ch.kind == RT_ANIM_NONE || (std::isfinite(ch.a) && std::isfinite(ch.k) && std::isfinite(ch.c));
+}
+// (first slot, count) of every node's subtree, from the leaf words
+AnimNodeRange node_ranges(const BvhNode *nodes, int id, std::vector<AnimNodeRange> &out) {
+    if (nodes[id].leaf) return out[id] = AnimNodeRange{nodes[id].leaf & 0xFFFFFF, nodes[id].leaf >> 24};
+    const AnimNodeRange l = node_ranges(nodes, id + 1, out);
+    int right = id + 1;  // the node after the left subtree
+    right = nodes[right].skip;
+    const AnimNodeRange r = node_ranges(nodes, right, out);
+    return out[id] = AnimNodeRange{l.first, l.count + r.count};
+}
+
+}  // namespace
+
+int anim_plan(const char *who_c, const rt_object *base, const rt_object_anim *anim, const rt_anim_channel *radius,
+              int n_objs, const rt_material *mats, int n_mats, const rt_light *lights, int n_lights, int max_frames,
+              bool spheres, AnimPlan &plan) {
+    const std::string who(who_c);
+    if (!base || !anim || n_objs <= 0 || n_objs > RT_MAX_OBJECTS || !mats || n_mats <= 0 || n_mats > RT_MAX_MATERIALS ||
+        n_lights < 0 || n_lights > RT_MAX_LIGHTS || (n_lights > 0 && !lights)) {
+        set_error(who + ": bad arguments");
+        return RT_ERR_INVALID;
+    }
+    if (max_frames < 1 || max_frames > RT_MAX_BATCH) {
+        set_error(who + ": max_frames outside [1, " + std::to_string(RT_MAX_BATCH) + "]");
+        return RT_ERR_INVALID;
+    }
+    const rt_anim_channel none{};
+    std::vector<rt_object> bound(base, base + n_objs);  // every object where it reaches farthest
+    std::vector<char> moving_sphere(n_objs, 0);
+    int n_sph = 0, n_moving = 0;
+    bool time_bound = false, box_moves = false;
+    for (int i = 0; i < n_objs; ++i) {
+        const rt_anim_channel *c = &anim[i].scale;  // 7 channels, contiguous
+        const rt_anim_channel &rad = radius ? radius[i] : none;
+        for (int k = 0; k < 8; ++k) {
+            const int kind = k < 7 ? c[k].kind : rad.kind;
+            if (kind < RT_ANIM_NONE || kind > RT_ANIM_SIN_OFFSET) {
+                set_error(who + ": object " + std::to_string(i) + " has a channel of unknown kind " +
+                          std::to_string(kind));
+                return RT_ERR_INVALID;
+            }
+        }
+        const int kind = object_kind(base[i]);
+        n_sph += kind == 2;
+        if (anim_is_static(anim[i]) && rad.kind == RT_ANIM_NONE) continue;
+        if (kind != 1 && !spheres) {
+            set_error(who + ": object " + std::to_string(i) +
+                      " is not a box: channels are supported on box objects only (static spheres are fine)");
+            return RT_ERR_UNSUPPORTED;
+        }
+        if (kind == 0) {
+            set_error(who + ": object " + std::to_string(i) +
+                      " is a null object: channels are supported on boxes and spheres only");
+            return RT_ERR_UNSUPPORTED;
+        }
+        if (kind == 1) {  // (a radius channel on a box moves nothing the render reads)
+            if (anim_is_static(anim[i])) continue;
+            box_moves = true;
+            const double s = channel_bound(anim[i].scale, 1.0) * (1.0 + 1e-6);
+            for (int k = 0; k < 3; ++k) {
+                bound[i].box_mins[k] = static_cast<float>(std::fabs(double(base[i].box_mins[k])) * s * (1.0 + 1e-6));
+                bound[i].box_maxs[k] = static_cast<float>(std::fabs(double(base[i].box_maxs[k])) * s * (1.0 + 1e-6));
+                bound[i].position[k] =
+                    static_cast<float>(channel_bound(anim[i].position[k], base[i].position[k]) * (1.0 + 1e-6));
+                time_bound = time_bound || channel_grows(anim[i].position[k]);
+            }
+            time_bound = time_bound || channel_grows(anim[i].scale);
+            continue;
+        }
+        // a sphere moves by its position and radius channels (the render never
+        // reads a sphere's angles or box extents)
+        bool moves = rad.kind != RT_ANIM_NONE, finite = std::isfinite(base[i].radius) && channel_finite(rad) &&
+                                                        std::isfinite(base[i].radius * base[i].radius);
+        for (int k = 0; k < 3; ++k) {
+            moves = moves || anim[i].position[k].kind != RT_ANIM_NONE;
+            finite = finite && std::isfinite(base[i].position[k]) && channel_finite(anim[i].position[k]);
+        }
+        if (!moves) continue;
+        if (!finite) {
+            set_error(who + ": object " + std::to_string(i) +
+                      " is a moving sphere whose base position, radius or channel constants are not finite");
+            return RT_ERR_INVALID;
+        }
+        moving_sphere[i] = 1;
+        ++n_moving;
+        for (int k = 0; k < 3; ++k) {
+            bound[i].position[k] =
+                static_cast<float>(channel_bound(anim[i].position[k], base[i].position[k]) * (1.0 + 1e-6));
+            time_bound = time_bound || channel_grows(anim[i].position[k]);
+        }
+        bound[i].radius = static_cast<float>(channel_bound(rad, base[i].radius) * (1.0 + 1e-6));
+        time_bound = time_bound || channel_grows(rad);
+    }
+    const std::string limit = " has a moving sphere and " + std::to_string(n_sph) + " spheres: at most " +
+                              std::to_string(RT_GMASK_FROM) +
+                              " spheres may share a scene with a moving one (more need wide masks and candidate "
+                              "lists, which are not rebuilt on the device)";
+    if (n_moving > 0 && n_sph > RT_GMASK_FROM) {
+        set_error(who + ": the scene" + limit);
+        return RT_ERR_UNSUPPORTED;
+    }
+    const double extent = objects_extent(bound.data(), n_objs) * (1.0 + 1e-6);
+    std::vector<float4> &blob = plan.blob;
+    DeviceScene &ds = plan.ds;
+    int rc = build_scene(base, n_objs, mats, n_mats, lights, n_lights, blob, ds, true, extent);
+    if (rc != RT_OK) return rc;
+    const SceneLayout &L = ds.layout;
+    if ((static_cast<size_t>(L.blob_units) + view_units(L, false)) * sizeof(float4) > kMaxLds) {
+        set_error(who + ": scene needs more than 160 KiB of LDS");
+        return RT_ERR_UNSUPPORTED;
+    }
+    if (n_moving > 0 && (L.off_gmask >= 0 || ds.olist_eligible)) {  // (the layout's own word on the limit above)
+        set_error(who + ": the scene" + limit);
+        return RT_ERR_UNSUPPORTED;
+    }
+    // The room shape reads the one box's record and the lights (DeviceScene::
+    // room): a box without channels keeps the host's record (the kernel leaves
+    // it alone), so build_scene's decision stands; a moving box never claims it.
+    const bool static_room = L.n_boxes == 1 && !box_moves;
+    if (!static_room) ds.room = 0;
+    // the kernel's static table
+    AnimTable T{};
+    T.n_boxes = static_room ? 0 : L.n_boxes;
+    T.n_lights = n_lights;
+    T.n_spheres = L.n_spheres;
+    T.dmask_n = L.dmask_n;
+    T.dmask_bytes = L.dmask_bytes;
+    T.dmask_box = L.dmask_box;
+    T.extent = extent;
+    T.finite = 1;
+    T.n_bvh = L.n_bvh;
+    T.blob_spheres = L.off_spheres;
+    T.blob_smeta = L.off_smeta;
+    T.blob_bvh = L.off_bvh;
+    T.blob_cone = L.off_cone;
+    std::vector<rt_object> tb;
+    std::vector<rt_object_anim> ta;
+    for (int i = 0; i < n_objs; ++i) {
+        const bool box = object_kind(base[i]) == 1;
+        bool fin = std::isfinite(base[i].radius);
+        for (int k = 0; k < 3 && !box; ++k)
+            fin = fin && std::isfinite(base[i].position[k]) && std::isfinite(base[i].box_mins[k]) &&
+                  std::isfinite(base[i].box_maxs[k]);
+        if (!fin) T.finite = 0;
+        if (box && !static_room) {
+            tb.push_back(base[i]);
+            ta.push_back(anim[i]);
+        }
+    }
+    // the moving spheres, by their slot in the template's leaf order
+    std::vector<AnimSphere> ts;
+    const SphereMeta *smeta = reinterpret_cast<const SphereMeta *>(blob.data() + L.off_smeta);
+    uint64_t moving_bits = 0;
+    // spheres the BVH covers: the finite ones, first in slot order (build_bvh)
+    const BvhNode *nodes = reinterpret_cast<const BvhNode *>(blob.data() + L.off_bvh);
+    std::vector<AnimNodeRange> ranges(std::max(L.n_bvh, 1), AnimNodeRange{0, 0});
+    if (L.n_bvh > 0) node_ranges(nodes, 0, ranges);
+    const int n_in_bvh = L.n_bvh > 0 ? ranges[0].count : 0;
+    for (int s = 0; s < L.n_spheres && n_moving > 0; ++s) {
+        const int i = smeta[s].obj_index;
+        if (!moving_sphere[i]) continue;
+        if (s >= n_in_bvh) {  // (unreachable: a moving sphere's base is finite)
+            set_error(who + ": object " + std::to_string(i) + " is a moving sphere outside the BVH");
+            return RT_ERR_INVALID;
+        }
+        AnimSphere a{};
+        std::memcpy(a.position, base[i].position, 12);
+        a.radius = base[i].radius;
+        for (int k = 0; k < 3; ++k) a.ch[k] = anim[i].position[k];
+        a.ch[3] = radius ? radius[i] : none;
+        a.slot = s;
+        ts.push_back(a);
+        moving_bits |= uint64_t{1} << s;
+    }
+    T.n_msph = static_cast<int32_t>(ts.size());
+    T.moving_slots = static_cast<uint32_t>(moving_bits);
+    std::vector<float4> tl(std::max(n_lights, 1));
+    const LightRec *lrec = reinterpret_cast<const LightRec *>(blob.data() + L.off_lights);
+    for (int j = 0; j < n_lights; ++j) {
+        const int32_t live = lrec[j].dead == 0.0f ? T.n_live++ : -1;
+        tl[j] = make_float4(lights[j].position[0], lights[j].position[1], lights[j].position[2], 0.0f);
+        std::memcpy(&tl[j].w, &live, 4);
+    }
+    std::vector<double> tc;
+    std::vector<unsigned char> tm;
+    if (L.dmask_n > 0 && (L.dmask_box || !ts.empty())) {
+        const MaskConeTable mc = mask_cone_table(L.dmask_n);
+        const size_t texels = static_cast<size_t>(6) * L.dmask_n * L.dmask_n;
+        tc.resize(5 * texels);
+        for (size_t t = 0; t < texels; ++t) {
+            for (int k = 0; k < 3; ++k) tc[5 * t + k] = mc.w[3 * t + k];
+            tc[5 * t + 3] = mc.ca[t];
+            tc[5 * t + 4] = mc.sa[t];
+        }
+        // the template masks: the static spheres' bits alone
+        tm.resize(static_cast<size_t>(T.n_live) * texels * L.dmask_bytes);
+        unsigned char *m = reinterpret_cast<unsigned char *>(blob.data() + L.off_dmask);
+        uint64_t keep = L.n_spheres >= 64 ? ~uint64_t{0} : ((uint64_t{1} << L.n_spheres) - 1u);
+        keep &= ~moving_bits;
+        for (size_t t = 0; t < static_cast<size_t>(T.n_live) * texels; ++t) {
+            uint64_t v = 0;
+            std::memcpy(&v, m + t * L.dmask_bytes, L.dmask_bytes);
+            v &= keep;
+            std::memcpy(m + t * L.dmask_bytes, &v, L.dmask_bytes);
+        }
+        std::memcpy(tm.data(), m, tm.size());
+    }
+    auto align16 = [](size_t x) { return (x + 15) / 16 * 16; };
+    size_t at = align16(sizeof(AnimTable));
+    T.off_base = static_cast<int32_t>(at);  at = align16(at + tb.size() * sizeof(rt_object));
+    T.off_anim = static_cast<int32_t>(at);  at = align16(at + ta.size() * sizeof(rt_object_anim));
+    T.off_light = static_cast<int32_t>(at); at = align16(at + tl.size() * sizeof(float4));
+    T.off_cone = static_cast<int32_t>(at);  at = align16(at + tc.size() * sizeof(double));
+    T.off_mask = static_cast<int32_t>(at);  at = align16(at + tm.size());
+    T.off_msph = static_cast<int32_t>(at);  at = align16(at + ts.size() * sizeof(AnimSphere));
+    T.off_node = static_cast<int32_t>(at);  at = align16(at + ranges.size() * sizeof(AnimNodeRange));
+    std::vector<unsigned char> &table = plan.table;
+    table.assign(at + 16, 0);
+    std::memcpy(table.data(), &T, sizeof T);
+    if (!tb.empty()) std::memcpy(table.data() + T.off_base, tb.data(), tb.size() * sizeof(rt_object));
+    if (!ta.empty()) std::memcpy(table.data() + T.off_anim, ta.data(), ta.size() * sizeof(rt_object_anim));
+    std::memcpy(table.data() + T.off_light, tl.data(), tl.size() * sizeof(float4));
+    if (!tc.empty()) std::memcpy(table.data() + T.off_cone, tc.data(), tc.size() * sizeof(double));
+    if (!tm.empty()) std::memcpy(table.data() + T.off_mask, tm.data(), tm.size());
+    if (!ts.empty()) std::memcpy(table.data() + T.off_msph, ts.data(), ts.size() * sizeof(AnimSphere));
+    std::memcpy(table.data() + T.off_node, ranges.data(), ranges.size() * sizeof(AnimNodeRange));
+    plan.tab = T;
+    plan.time_bound = time_bound;
+    return RT_OK;
+}
+
+void anim_apply_spheres_host(const AnimPlan &plan, float time, std::vector<float4> &blob) {
+    const AnimTable &T = plan.tab;
+    if (T.n_msph == 0) return;
+    const unsigned char *table = plan.table.data();
+    const AnimSphere *msph = reinterpret_cast<const AnimSphere *>(table + T.off_msph);
+    const float4 *light = reinterpret_cast<const float4 *>(table + T.off_light);
+    SphereRec *sph = reinterpret_cast<SphereRec *>(blob.data() + T.blob_spheres);
+    SphereMeta *smeta = reinterpret_cast<SphereMeta *>(blob.data() + T.blob_smeta);
+    // 1. records
+    for (int i = 0; i < T.n_msph; ++i) {
+        float rad;
+        anim_sphere_records(msph[i], time, sph[msph[i].slot], rad);
+        smeta[msph[i].slot].radius = rad;
+    }
+    // 2. the BVH's bounds and the ShadowCone entries
+    const AnimNodeRange *range = reinterpret_cast<const AnimNodeRange *>(table + T.off_node);
+    BvhNode *bvh = reinterpret_cast<BvhNode *>(blob.data() + T.blob_bvh);
+    std::vector<AnimSphereBox> sbox(T.n_spheres);
+    for (int s = 0; s < T.n_spheres; ++s) sbox[s] = anim_sphere_box(sph[s], smeta[s].radius, T.extent);
+    for (int n = 0; n < T.n_bvh; ++n) anim_node_bounds(sbox.data(), range[n], bvh[n].lo, bvh[n].hi);
+    if (T.blob_cone >= 0) {
+        ShadowCone *scone = reinterpret_cast<ShadowCone *>(blob.data() + T.blob_cone);
+        for (int i = 0; i < T.n_msph; ++i)
+            for (int j = 0; j < T.n_lights; ++j) {
+                const int slot = msph[i].slot;
+                const float lp[3] = {light[j].x, light[j].y, light[j].z};
+                scone[j * T.n_spheres + slot] = anim_shadow_cone(sph[slot], smeta[slot].radius, lp);
+            }
+    }
+    // 3. the moving spheres' mask bits
+    if (T.dmask_n <= 0) return;
+    const size_t texels = static_cast<size_t>(6) * T.dmask_n * T.dmask_n;
+    const double *cone_tab = reinterpret_cast<const double *>(table + T.off_cone);
+    unsigned char *dmask = reinterpret_cast<unsigned char *>(blob.data() + plan.ds.layout.off_dmask);
+    for (int j = 0; j < T.n_lights; ++j) {
+        int32_t li;
+        std::memcpy(&li, &light[j].w, 4);
+        if (li < 0) continue;
+        const float lp[3] = {light[j].x, light[j].y, light[j].z};
+        for (int i = 0; i < T.n_msph; ++i) {
+            const SphereRec &s = sph[msph[i].slot];
+            const float ball[4] = {s.cx, s.cy, s.cz, smeta[msph[i].slot].radius};
+            const MaskCone c = anim_mask_cone(ball, lp, msph[i].slot);
+            for (size_t t = 0; t < texels; ++t) {
+                if (!anim_texel_hit(cone_tab + 5 * t, c)) continue;
+                unsigned char *m = dmask + (static_cast<size_t>(li) * texels + t) * T.dmask_bytes;
+                uint64_t v = 0;
+                std::memcpy(&v, m, T.dmask_bytes);
+                v |= uint64_t{1} << c.bit;
+                std::memcpy(m, &v, T.dmask_bytes);
+            }
+        }
+    }
+}
+
 }  // namespace rtamd
+
+extern "C" {
+
+// Development hook (host only, not part of include/rt.h): the code and
+// message rt_anim_create2 would return for this description (rt_anim_create
+// when `boxes_only`), without a device.
+int rt_debug_anim_validate(const rt_object *base, const rt_object_anim *anim, const rt_anim_channel *radius, int n_objs,
+                           const rt_material *mats, int n_mats, const rt_light *lights, int n_lights, int max_frames,
+                           int boxes_only) {
+    AnimPlan plan;
+    return anim_plan(boxes_only ? "rt_anim_create" : "rt_anim_create2", base, anim, boxes_only ? nullptr : radius,
+                     n_objs, mats, n_mats, lights, n_lights, max_frames, !boxes_only, plan);
+}
+
+// Development hook (host only, not part of include/rt.h): the slot blob of
+// rt_anim_create2's scene at `time` as the host makes it (rt_debug_anim_blob's
+// layout). The spheres' parts — records, BVH bounds, ShadowCone entries, mask
+// bits — come from the animate kernel's own functions (rt_anim.h) applied to
+// the template; the boxes' records, planes and mask bits are build_scene's of
+// the objects at `time`. meta (24 ints): rt_debug_scene_blob's. Returns the
+// blob's bytes (copied when they fit in cap), or a negative RT_ERR_*.
+long long rt_debug_anim_host_blob(const rt_object *base, const rt_object_anim *anim, const rt_anim_channel *radius,
+                                  int n_objs, const rt_material *mats, int n_mats, const rt_light *lights,
+                                  int n_lights, float time, void *out, long long cap, int32_t *meta) {
+    AnimPlan plan;
+    int rc = anim_plan("rt_anim_create2", base, anim, radius, n_objs, mats, n_mats, lights, n_lights, 1, true, plan);
+    if (rc != RT_OK) return rc;
+    if (plan.time_bound && !(std::fabs(time) <= kAnimTimeBound)) {
+        set_error("rt_debug_anim_host_blob: time outside the scene's range");
+        return RT_ERR_UNSUPPORTED;
+    }
+    std::vector<float4> blob = plan.blob;
+    anim_apply_spheres_host(plan, time, blob);
+    const SceneLayout &L = plan.ds.layout;
+    if (plan.tab.n_boxes > 0) {
+        std::vector<rt_object> objs(n_objs);
+        if ((rc = rt_animate_objects2(base, anim, radius, n_objs, time, objs.data())) != RT_OK) return rc;
+        // (a sphere keeps its base's kind here: its radius at `time` plays no part in the boxes' data)
+        for (int i = 0; i < n_objs; ++i)
+            if (object_kind(base[i]) != 1) objs[i] = base[i];
+        std::vector<float4> at;
+        DeviceScene ds;
+        if ((rc = build_scene(objs.data(), n_objs, mats, n_mats, lights, n_lights, at, ds, true, plan.tab.extent)) != RT_OK)
+            return rc;
+        if (std::memcmp(&ds.layout, &L, sizeof L) != 0) {
+            set_error("rt_debug_anim_host_blob: the boxes at this time change the layout");
+            return RT_ERR_UNSUPPORTED;
+        }
+        std::memcpy(blob.data() + L.off_boxes, at.data() + L.off_boxes, static_cast<size_t>(L.n_boxes) * sizeof(BoxRec));
+        if (L.off_bplane >= 0)
+            std::memcpy(blob.data() + L.off_bplane, at.data() + L.off_bplane,
+                        static_cast<size_t>(L.n_boxes) * L.n_lights * sizeof(float4));
+        if (L.dmask_box) {
+            const size_t n = static_cast<size_t>(plan.tab.n_live) * 6 * L.dmask_n * L.dmask_n;
+            unsigned char *m = reinterpret_cast<unsigned char *>(blob.data() + L.off_dmask);
+            const unsigned char *h = reinterpret_cast<const unsigned char *>(at.data() + L.off_dmask);
+            const uint64_t box_bits = ~((uint64_t{1} << L.n_spheres) - 1u);
+            for (size_t t = 0; t < n; ++t) {
+                uint64_t v = 0, w = 0;
+                std::memcpy(&v, m + t * L.dmask_bytes, L.dmask_bytes);
+                std::memcpy(&w, h + t * L.dmask_bytes, L.dmask_bytes);
+                v |= w & box_bits;
+                std::memcpy(m + t * L.dmask_bytes, &v, L.dmask_bytes);
+            }
+        }
+    }
+    const long long bytes = static_cast<long long>(blob.size() * sizeof(float4));
+    if (out && cap >= bytes) std::memcpy(out, blob.data(), static_cast<size_t>(bytes));
+    if (meta) {
+        const int32_t m[24] = {L.blob_units, L.off_spheres, L.off_smeta, L.off_boxes, L.off_mats,
+                               L.off_lights, L.off_lightmat, L.off_bvh, L.n_bvh, L.off_blink, L.off_cone,
+                               L.off_dmask, L.dmask_n, L.dmask_bytes, L.off_gmask, L.gmask_words,
+                               L.off_glist, L.n_spheres, L.n_boxes, L.n_mats, L.n_lights, L.off_olist,
+                               0, 0};
+        std::memcpy(meta, m, sizeof m);
+    }
+    return bytes;
+}
+
+}  // extern "C"

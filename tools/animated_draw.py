@@ -10,6 +10,13 @@ interleaved repeats, medians.
      against rt_render_batch_animated (which also runs the animate kernel for
      the 256 frames), stream time between two events.
 
+--scene config2: the headline workload instead, 1920x1080, depth 0, the room
+and 16 spheres, every sphere on SIN_OFFSET position channels and every third
+one on a radius channel too (rt_anim_create2); A moves the scene with
+rt_animate_objects2, and C gains a row for config 2's static 256-frame launch
+(rt_render_batch of one scene: the persistent grid, which a batch of per-slot
+blobs does not take).
+
 Run it under a time limit of its own, e.g.
   timeout -k 10 300 python tools/animated_draw.py | tee profiles/<name>.log
 """
@@ -26,32 +33,59 @@ import torch  # noqa: E402
 import openglraytracer_amd as rt  # noqa: E402
 
 W, H, DEPTH, N, BATCH = 1280, 720, 0, 200, 256
+CONFIG2 = sys.argv[1:] == ["--scene", "config2"]
+assert CONFIG2 or not sys.argv[1:], "usage: animated_draw.py [--scene config2]"
+if CONFIG2:
+    W, H = 1920, 1080
 
 
 def frame_time(k):
     return k / 60.0
 
 
+def config2_animation():
+    """Config 2's objects, every sphere moving about its place, every third breathing."""
+    from openglraytracer_amd.abi import AnimChannel, ObjectAnim, RT_ANIM_SIN_OFFSET
+    rng = np.random.default_rng(2)
+    base = rt.bench_objects(16)
+    anim, radius = [ObjectAnim() for _ in base], [AnimChannel() for _ in base]
+    for i in range(1, len(base)):
+        for k in range(3):
+            anim[i].position[k] = AnimChannel(RT_ANIM_SIN_OFFSET, float(rng.uniform(0.3, 1.5)),
+                                              float(rng.uniform(0.3, 2.0)), base[i].position[k])
+        if i % 3 == 0:
+            radius[i] = AnimChannel(RT_ANIM_SIN_OFFSET, 0.25, float(rng.uniform(0.3, 2.0)), base[i].radius)
+    return base, anim, radius
+
+
 def main():
     ctx = rt.Context(0)
     print(rt.lib().rt_version().decode(), flush=True)
-    base, anim = rt.reference_animation()
-    live = rt.Scene(ctx, rt.reference_objects(0.0))
-    an1 = rt.Anim(ctx, base, anim, max_frames=1)
-    an4 = rt.Anim(ctx, base, anim, max_frames=4)
-    anb = rt.Anim(ctx, base, anim, max_frames=BATCH)
+    if CONFIG2:
+        base, anim, radius = config2_animation()
+        kw = {"radius": radius}
+
+        def objects_at(t):
+            return rt.animate_objects(base, anim, t, radius)
+    else:
+        base, anim = rt.reference_animation()
+        kw, objects_at = {}, rt.reference_objects
+    live = rt.Scene(ctx, objects_at(0.0))
+    an1 = rt.Anim(ctx, base, anim, max_frames=1, **kw)
+    an4 = rt.Anim(ctx, base, anim, max_frames=4, **kw)
+    anb = rt.Anim(ctx, base, anim, max_frames=BATCH, **kw)
     out = torch.empty((H, W, 4), dtype=torch.float32, device="cuda")
     outs = [torch.empty((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(4)]
     big = torch.empty((BATCH, H, W, 4), dtype=torch.float32, device="cuda")
     stream = torch.cuda.Stream()
     times = [frame_time(k) for k in range(BATCH)]
     views = [rt.make_view(None, t) for t in times]
-    scenes = [rt.Scene(ctx, rt.reference_objects(t)) for t in times]
+    scenes = [rt.Scene(ctx, objects_at(t)) for t in times]
     torch.cuda.synchronize()
 
     def draw_a(k):
         t = frame_time(k)
-        live.update(rt.reference_objects(t))
+        live.update(objects_at(t))
         rt.render_batch(ctx, live, out.data_ptr(), W, H, DEPTH, [rt.make_view(None, t)])
 
     def draw_b(k):
@@ -93,7 +127,21 @@ def main():
     def batch_animated():
         rt.render_batch_animated(ctx, anb, big.data_ptr(), W, H, DEPTH, times, stream=stream.cuda_stream)
 
-    batch_prebuilt()
+    def batch_static():
+        rt.render_batch(ctx, scenes[0], big.data_ptr(), W, H, DEPTH, views, stream=stream.cuda_stream)
+
+    # Host-built scenes of moving spheres need not share a layout (the BVH's
+    # node count follows the spheres' positions), and rt_render_batch_scenes
+    # then refuses them: the row is left out, and frame 200 is checked against
+    # its own scene's render.
+    prebuilt = True
+    try:
+        batch_prebuilt()
+    except rt.RTError as e:
+        prebuilt = False
+        print("C  rt_render_batch_scenes refuses the prebuilt scenes: %s" % e, flush=True)
+        rt.render_batch(ctx, scenes[200], big.data_ptr() + 200 * H * W * 16, W, H, DEPTH, [views[200]],
+                        stream=stream.cuda_stream)
     torch.cuda.synchronize()
     want = big[200].cpu().numpy().copy()
     big.zero_()
@@ -102,12 +150,13 @@ def main():
     assert np.array_equal(big[200].cpu().numpy(), want), "C: prebuilt and animated differ"
 
     ctx.set_timing(False)  # (no per-launch events: the loops time themselves)
-    res = {k: [] for k in ("A", "B", "B_async", "C_prebuilt", "C_animated", "C_animated_host")}
+    res = {k: [] for k in ("A", "B", "B_async", "C_static", "C_prebuilt", "C_animated", "C_animated_host")}
     for rep in range(3):
         res["A"].append(wall(draw_a))
         res["B"].append(wall(draw_b))
         res["B_async"].append(wall(draw_b_async, drain=True))
-        res["C_prebuilt"].append(events(batch_prebuilt))
+        res["C_static"].append(events(batch_static) if CONFIG2 else 0.0)
+        res["C_prebuilt"].append(events(batch_prebuilt) if prebuilt else float("nan"))
         res["C_animated"].append(events(batch_animated))
         t0 = time.perf_counter()
         batch_animated()
@@ -120,9 +169,13 @@ def main():
     print("A  rt_scene_update + synchronous render      %8.2f" % med["A"])
     print("B  rt_render_animated, synchronous           %8.2f  (%.2fx of A)" % (med["B"], med["B"] / med["A"]))
     print("B' rt_render_animated, one stream, 4 slots   %8.2f" % med["B_async"])
-    print("C  rt_render_batch_scenes, prebuilt scenes   %8.2f" % med["C_prebuilt"])
-    print("C  rt_render_batch_animated                  %8.2f  (%.3fx of prebuilt; host %.2f us per frame of the call)"
-          % (med["C_animated"], med["C_animated"] / med["C_prebuilt"], med["C_animated_host"]))
+    if CONFIG2:
+        print("C  rt_render_batch, one static scene         %8.2f" % med["C_static"])
+    if prebuilt:
+        print("C  rt_render_batch_scenes, prebuilt scenes   %8.2f" % med["C_prebuilt"])
+    print("C  rt_render_batch_animated                  %8.2f  (%.3fx of %s; host %.2f us per frame of the call)"
+          % (med["C_animated"], med["C_animated"] / med["C_prebuilt" if prebuilt else "C_static"],
+             "prebuilt" if prebuilt else "the static scene", med["C_animated_host"]))
     for s in scenes:
         s.close()
     for a in (an1, an4, anb):

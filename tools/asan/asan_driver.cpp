@@ -21,6 +21,14 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
                 double extent_floor = 0.0);
 int build_origin_lists_for(const std::vector<float4> &host, const DeviceScene &ds, std::vector<uint8_t> &olist);
 }  // namespace rtamd
+// host-only development hooks (rt_scene.cpp)
+extern "C" int rt_debug_anim_validate(const rt_object *base, const rt_object_anim *anim, const rt_anim_channel *radius,
+                                      int n_objs, const rt_material *mats, int n_mats, const rt_light *lights,
+                                      int n_lights, int max_frames, int boxes_only);
+extern "C" long long rt_debug_anim_host_blob(const rt_object *base, const rt_object_anim *anim,
+                                             const rt_anim_channel *radius, int n_objs, const rt_material *mats,
+                                             int n_mats, const rt_light *lights, int n_lights, float time, void *out,
+                                             long long cap, int32_t *meta);
 
 namespace {
 
@@ -100,6 +108,59 @@ int main(int argc, char **argv) {
                                ds, true) != RT_OK)
             return 1;
         ++g_built;
+    }
+    // moving spheres (rt_anim_create2's host side, the sphere phases' arithmetic
+    // of rt_anim.h on the template blob): config 2's scene with every sphere
+    // moving and some breathing, and the shipped scene's boxes with its sphere
+    // moving (box bits beside the sphere's); then the refusals
+    for (int which = 0; which < 2; ++which) {
+        std::vector<rt_object> base(17);
+        std::vector<rt_object_anim> anim(17);
+        int n = 17;
+        if (which == 0) {
+            if (rt_bench_objects(16, 3, base.data()) != RT_OK) return 1;
+            std::memset(anim.data(), 0, anim.size() * sizeof(rt_object_anim));
+        } else {
+            n = RT_REFERENCE_OBJECTS;
+            if (rt_reference_animation(base.data(), anim.data()) != RT_OK) return 1;
+        }
+        std::vector<rt_anim_channel> radius(n, rt_anim_channel{RT_ANIM_NONE, 0.0f, 0.0f, 0.0f});
+        for (int i = 0; i < n; ++i) {
+            const rt_object &o = base[i];
+            if (o.box_mins[0] != 0.0f || o.box_maxs[0] != 0.0f) continue;  // (the boxes of these scenes)
+            for (int k = 0; k < 3; ++k)
+                anim[i].position[k] = rt_anim_channel{RT_ANIM_SIN_OFFSET, 0.5f + 0.1f * k, 0.7f + 0.05f * i, o.position[k]};
+            if (i % 3 == 0) radius[i] = rt_anim_channel{RT_ANIM_SIN, 1.1f, 0.9f, 0.0f};  // (through 0, negative too)
+        }
+        if (rt_debug_anim_validate(base.data(), anim.data(), radius.data(), n, mats, RT_REFERENCE_MATERIALS, lights,
+                                   RT_REFERENCE_LIGHTS, 4, 0) != RT_OK)
+            return 1;
+        for (float t : {0.0f, 1.25f, -40.0f}) {
+            int32_t meta[24];
+            const long long bytes = rt_debug_anim_host_blob(base.data(), anim.data(), radius.data(), n, mats,
+                                                            RT_REFERENCE_MATERIALS, lights, RT_REFERENCE_LIGHTS, t,
+                                                            nullptr, 0, meta);
+            if (bytes <= 0) return 1;
+            std::vector<unsigned char> out(static_cast<size_t>(bytes));
+            if (rt_debug_anim_host_blob(base.data(), anim.data(), radius.data(), n, mats, RT_REFERENCE_MATERIALS,
+                                        lights, RT_REFERENCE_LIGHTS, t, out.data(), bytes, meta) != bytes)
+                return 1;
+            ++g_built;
+        }
+        radius[n - 1].kind = 9;
+        if (rt_debug_anim_validate(base.data(), anim.data(), radius.data(), n, mats, RT_REFERENCE_MATERIALS, lights,
+                                   RT_REFERENCE_LIGHTS, 4, 0) != RT_ERR_INVALID)
+            return 1;
+    }
+    {
+        std::vector<rt_object> base(34);
+        std::vector<rt_object_anim> anim(34);
+        std::memset(anim.data(), 0, anim.size() * sizeof(rt_object_anim));
+        if (rt_bench_objects(33, 3, base.data()) != RT_OK) return 1;
+        anim[5].position[0] = rt_anim_channel{RT_ANIM_RATE, 0.0f, 0.01f, 0.0f};
+        if (rt_debug_anim_validate(base.data(), anim.data(), nullptr, 34, mats, RT_REFERENCE_MATERIALS, lights,
+                                   RT_REFERENCE_LIGHTS, 1, 0) != RT_ERR_UNSUPPORTED)
+            return 1;
     }
     // image dump and RGBA8 packing (NaN / inf / negative values)
     std::vector<float> img(37 * 11 * 4);

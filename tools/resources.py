@@ -56,8 +56,9 @@ def kernel_name(mangled):
         if launch != "0":
             name += ",%s" % launch
         return name + ">"
-    if "animate_kernel" in mangled:
-        return "animate_kernel"
+    m = re.search(r"animate_kernelILb([01])E", mangled)
+    if m:  # the instance with the sphere phases (rt_anim.hip), or the box phases alone
+        return "animate_kernel<%s>" % ("true" if m.group(1) == "1" else "false")
     return mangled
 
 
@@ -138,7 +139,9 @@ TABLE = [
     ("depth 2, general", "render_kernel<2,false,false>"),
     ("depth 4, config 4 (room, wide masks, origin lists)", "render_kernel<4,false,false,48>"),
     ("depth 4, general", "render_kernel<4,false,false>"),
-    ("the animate kernel (one work-group per frame ahead of an animated render, rt_anim.hip)", "animate_kernel"),
+    ("the animate kernel (one work-group per frame ahead of an animated render, rt_anim.hip), boxes only",
+     "animate_kernel<false>"),
+    ("the animate kernel with the sphere phases (scenes with moving spheres)", "animate_kernel<true>"),
 ]
 
 
