@@ -1,11 +1,14 @@
 // rt_anim.h — a scene as a function of `time` (include/rt.h, rt_anim): the
 // channel arithmetic the host (rt_animate_objects, rt_scene.cpp) and the
-// animate kernel (rt_anim.hip) share, and the kernel's argument block.
+// animate kernel (rt_anim.hip) share, and the kernel's argument block. What
+// follows from an object once it is placed — records, culling data — is
+// rt_cull.h's, the text the scene builder runs too.
 #pragma once
 
 #include <cmath>
 #include <vector>
 
+#include "rt_cull.h"
 #include "rt_glmath.h"
 #include "rt_internal.h"
 
@@ -60,8 +63,8 @@ inline bool anim_is_static(const rt_object_anim &an) {
 constexpr float kAnimTimeBound = 1.0e4f;
 
 // ---- moving spheres (rt_anim_create2) ---------------------------------------
-// One text for the host (rt_animate_objects2, the host hook
-// rt_debug_anim_host_blob) and the animate kernel's sphere phases.
+// One text for the host (rt_animate_objects2, anim_apply_spheres_host) and
+// the animate kernel's sphere phases.
 //
 // A moving sphere: its base centre and radius, the channels that move it
 // (x, y, z, radius) and its slot in the template's leaf order (fixed at
@@ -86,28 +89,15 @@ __host__ __device__ inline void anim_sphere_records(const AnimSphere &s, float t
 struct AnimNodeRange {
     int32_t first, count;
 };
-// A sphere's box in float64 with build_bvh's margin (the table's extent bound
-// stands in for the scene's: a larger margin only widens the box). The radius
-// is the larger of sqrt(rr), what the intersection sees, and |radius|.
-struct AnimSphereBox {
-    double lo[3], hi[3];
-};
-__host__ __device__ inline AnimSphereBox anim_sphere_box(const SphereRec &s, float abs_radius, double extent) {
-    const double c[3] = {s.cx, s.cy, s.cz};
-    const double r = fmax(sqrt(static_cast<double>(s.rr)), static_cast<double>(abs_radius));
-    double mag = 0.0;
-    for (int a = 0; a < 3; ++a) mag = fmax(mag, fabs(c[a]) + r);
-    const double margin = 1e-3 + 1e-4 * fmax(mag, extent);
-    AnimSphereBox b;
-    for (int a = 0; a < 3; ++a) {
-        b.lo[a] = c[a] - r - margin;
-        b.hi[a] = c[a] + r + margin;
-    }
-    return b;
+// The box the refit gives a sphere: its radius the larger of sqrt(rr), what
+// the intersection sees, and |radius|; the table's extent bound stands in for
+// the scene's.
+__host__ __device__ inline SphereBox anim_sphere_box(const SphereRec &s, float abs_radius, double extent) {
+    return sphere_box(s, fmax(sqrt(static_cast<double>(s.rr)), static_cast<double>(abs_radius)), extent);
 }
 // The node's bounds, refitted: the union of its subtree's sphere boxes (one
 // per sphere slot), rounded outward to float32.
-__host__ __device__ inline void anim_node_bounds(const AnimSphereBox *box, AnimNodeRange nr, float lo[3], float hi[3]) {
+__host__ __device__ inline void anim_node_bounds(const SphereBox *box, AnimNodeRange nr, float lo[3], float hi[3]) {
     double l[3] = {1e300, 1e300, 1e300}, h[3] = {-1e300, -1e300, -1e300};
     for (int s = nr.first; s < nr.first + nr.count; ++s)
         for (int a = 0; a < 3; ++a) {
@@ -118,56 +108,6 @@ __host__ __device__ inline void anim_node_bounds(const AnimSphereBox *box, AnimN
         lo[a] = nextafterf(static_cast<float>(l[a]), -HUGE_VALF);
         hi[a] = nextafterf(static_cast<float>(h[a]), HUGE_VALF);
     }
-}
-// build_scene's ShadowCone of a sphere seen from a light (float64).
-__host__ __device__ inline ShadowCone anim_shadow_cone(const SphereRec &s, float abs_radius, const float light[3]) {
-    ShadowCone c = {{0.0f, 0.0f, 0.0f}, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    const double v[3] = {double(s.cx) - light[0], double(s.cy) - light[1], double(s.cz) - light[2]};
-    const double d = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    const double rp = double(abs_radius) + 0.021 + 1e-3 * d;
-    if (!(std::isfinite(d) && std::isfinite(rp)) || d <= rp) {
-        c.near = 1.0f;  // always a candidate
-        return c;
-    }
-    for (int r = 0; r < 3; ++r) c.v[r] = static_cast<float>(v[r] / d);
-    c.far = static_cast<float>(d - rp);
-    const double sp = rp / d;
-    c.sph = static_cast<float>(sp);
-    c.cph = static_cast<float>(sqrt(fmax(0.0, 1.0 - sp * sp)));
-    return c;
-}
-// The cone of a ball (centre, radius: a sphere, or a box's bounding sphere)
-// seen from a live light, for the direction masks (build_direction_masks):
-// axis, cos / sin of the half-angle + 1e-3, or every direction; `bit`: the
-// ball's mask bit.
-struct MaskCone {
-    double ax[3], ch, sh;
-    int32_t every, bit;
-};
-static_assert(sizeof(MaskCone) == 48, "MaskCone layout");
-__host__ __device__ inline MaskCone anim_mask_cone(const float ball[4], const float light[3], int bit) {
-    MaskCone c = {{0.0, 0.0, 0.0}, 0.0, 0.0, 0, bit};
-    const double v[3] = {double(ball[0]) - double(light[0]), double(ball[1]) - double(light[1]),
-                         double(ball[2]) - double(light[2])};
-    const double d = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    const double rp = double(ball[3]) + 0.021 + 1e-3 * d;
-    if (!(std::isfinite(d) && std::isfinite(rp)) || d <= rp) {
-        c.every = 1;
-    } else {
-        for (int k = 0; k < 3; ++k) c.ax[k] = v[k] / d;
-        const double half = asin(fmin(1.0, rp / d));
-        c.ch = cos(half + 1e-3);
-        c.sh = sin(half + 1e-3);
-    }
-    return c;
-}
-// The texel test (build_direction_masks): w = the texel's centre direction,
-// cos / sin of its half-angle (5 doubles).
-__host__ __device__ inline bool anim_texel_hit(const double *w, const MaskCone &c) {
-    // cos(alpha + half + 1e-3), less 1e-12 for rounding
-    const double lim = w[3] * c.ch - w[4] * c.sh - 1e-12;
-    const double dot = w[0] * c.ax[0] + w[1] * c.ax[1] + w[2] * c.ax[2];
-    return c.every != 0 || dot >= lim;
 }
 
 // The animate kernel's static table (device memory, built by rt_anim_create):
@@ -234,8 +174,10 @@ struct AnimPlan {
 int anim_plan(const char *who, const rt_object *base, const rt_object_anim *anim, const rt_anim_channel *radius,
               int n_objs, const rt_material *mats, int n_mats, const rt_light *lights, int n_lights, int max_frames,
               bool spheres, AnimPlan &plan);
-// The sphere phases of the animate kernel on the host: rewrites, in `blob` (a
-// copy of plan.blob), what the kernel rewrites for the moving spheres.
+// The animate kernel's phases on the host, in plain loops over the plan's
+// table: rewrite, in `blob` (a copy of plan.blob), what the kernel rewrites
+// for the boxes and for the moving spheres.
+void anim_apply_boxes_host(const AnimPlan &plan, float time, std::vector<float4> &blob);
 void anim_apply_spheres_host(const AnimPlan &plan, float time, std::vector<float4> &blob);
 int object_kind_of(const rt_object &o);
 // bound on |coordinate| of the finite objects (build_scene's BVH and plane margins)

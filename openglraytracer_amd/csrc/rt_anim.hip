@@ -17,7 +17,7 @@
 //      static spheres' template mask.
 // Scenes with moving spheres (rt_anim_create2) run the kernel's second
 // instance, animate_kernel<true>, which adds in the same phases, with the
-// arithmetic of rt_anim.h (the text the host runs):
+// arithmetic of rt_anim.h and rt_cull.h (the text the host runs):
 //   1. one lane per moving sphere: its SphereRec and SphereMeta::radius; one
 //      lane per sphere slot, moving or not: its float64 box with build_bvh's
 //      margin, in LDS;
@@ -29,9 +29,11 @@
 //   3. the moving spheres' bits in the direction masks, also in scenes
 //      without box bits.
 // Box-only scenes keep animate_kernel<false>, whose code carries none of that.
-// The culling data (light_inside, planes, mask bits) use build_scene's
-// inequalities and margins in float64; they need not equal the host's bit for
-// bit (the device's double sin / cos may differ in the last place) and are as
+// Every record and every culling term (light_inside, balls, planes, cones,
+// mask bits, BVH boxes) is rt_cull.h's function of the object, the text
+// build_scene runs; the loops, the table and the stores are this file's. What
+// passes through the float64 rotation need not equal the host's bit for bit
+// (the device's double sin / cos may differ in the last place) and is as
 // conservative: culling changes no pixel. Barriers only between the phases;
 // every store is a plain vector store.
 #include <hip/hip_runtime.h>
@@ -47,38 +49,13 @@ namespace {
 constexpr int kAnimThreads = 256;
 
 // LDS: [flag, 16 B][n float4 balls][n x n_live MaskCone][n_spheres
-// AnimSphereBox, scenes with a moving sphere], n = the balls with mask bits
+// SphereBox, scenes with a moving sphere], n = the balls with mask bits
 // the kernel recomputes (anim_mask_balls: the boxes' bounding spheres, then
 // the moving spheres)
 __host__ __device__ inline size_t lds_spheres_at() { return 16; }
 __host__ __device__ inline size_t lds_cones_at(int n_balls) { return 16 + static_cast<size_t>(n_balls) * 16; }
 __host__ __device__ inline size_t lds_boxes_at(int n_balls, int n_live) {
     return lds_cones_at(n_balls) + static_cast<size_t>(n_balls) * n_live * sizeof(MaskCone);
-}
-
-// build_scene's float64 rotation of an object (culling only): Rz(yaw) Rx(pitch)
-// Ry(roll), each angle the float DEG_TO_RAD * deg; R[col][row].
-__device__ void rotation64(const float ang[3], double R[3][3]) {
-    auto rot = [](int axis, float deg, double r[3][3]) {
-        const double a = static_cast<double>(glf::kDegToRad * deg);
-        double c, s;
-        sincos(a, &s, &c);
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) r[i][j] = i == j ? 1.0 : 0.0;
-        if (axis == 0) { r[1][1] = c; r[1][2] = s; r[2][1] = -s; r[2][2] = c; }
-        if (axis == 1) { r[0][0] = c; r[0][2] = -s; r[2][0] = s; r[2][2] = c; }
-        if (axis == 2) { r[0][0] = c; r[0][1] = s; r[1][0] = -s; r[1][1] = c; }
-    };
-    auto mul = [](const double a[3][3], const double b[3][3], double r[3][3]) {
-        for (int c = 0; c < 3; ++c)
-            for (int w = 0; w < 3; ++w) r[c][w] = a[0][w] * b[c][0] + a[1][w] * b[c][1] + a[2][w] * b[c][2];
-    };
-    double z[3][3], x[3][3], y[3][3], zx[3][3];
-    rot(2, ang[1], z);
-    rot(0, ang[0], x);
-    rot(1, ang[2], y);
-    mul(z, x, zx);
-    mul(zx, y, R);
 }
 
 template <bool kSpheres>
@@ -96,7 +73,7 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
     int *bad = reinterpret_cast<int *>(lds);  // 1: an animated field the plane test looks at is not finite
     float4 *bsph = reinterpret_cast<float4 *>(lds + lds_spheres_at());
     MaskCone *cones = reinterpret_cast<MaskCone *>(lds + lds_cones_at(n_balls));
-    AnimSphereBox *sbox = reinterpret_cast<AnimSphereBox *>(lds + lds_boxes_at(n_balls, T.n_live));
+    SphereBox *sbox = reinterpret_cast<SphereBox *>(lds + lds_boxes_at(n_balls, T.n_live));
     const rt_object *base = reinterpret_cast<const rt_object *>(p.table + T.off_base);
     const rt_object_anim *anim = reinterpret_cast<const rt_object_anim *>(p.table + T.off_anim);
     const float4 *light = reinterpret_cast<const float4 *>(p.table + T.off_light);
@@ -116,29 +93,10 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
     if (tid < kHalf) {
         for (int b = tid; b < nb; b += kHalf) {
             const rt_object o = animate_object(base[b], anim[b], time);
-            float L[16], W[16], N[9];
-            glf::box_transforms(o.position, o.angles, L, W, N);
-            BoxRec &rec = boxes[b];
-            float w2l[12];
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 4; ++c) {  // stored row-major
-                    w2l[r * 4 + c] = W[c * 4 + r];
-                    rec.w2l[r * 4 + c] = W[c * 4 + r];
-                    rec.l2w[r * 4 + c] = L[c * 4 + r];
-                }
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) rec.nrm[r * 3 + c] = N[c * 3 + r];
-            int translate_only = 1;
+            box_record(o, boxes[b]);
             bool finite = true;
-            for (int r = 0; r < 3; ++r) {
-                rec.mins[r] = o.box_mins[r];
-                rec.maxs[r] = o.box_maxs[r];
-                rec.w2l_w0[r] = w2l[r * 4 + 3] * 0.0f;
-                for (int c = 0; c < 3; ++c)
-                    if (w2l[r * 4 + c] != (r == c ? 1.0f : 0.0f)) translate_only = 0;
+            for (int r = 0; r < 3; ++r)
                 finite = finite && isfinite(o.position[r]) && isfinite(o.box_mins[r]) && isfinite(o.box_maxs[r]);
-            }
-            rec.translate_only = translate_only;
             if (!finite) *bad = 1;
         }
         // the static spheres' boxes for the BVH refit, one lane per slot
@@ -149,40 +107,16 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
     } else {
         for (int b = tid - kHalf; b < nb; b += kHalf) {
             const rt_object o = animate_object(base[b], anim[b], time);
-            // lights strictly inside the box by build_scene's margin (float64)
             double R[3][3];
             rotation64(o.angles, R);
             uint32_t inside = 0;
             for (int j = 0; j < nl && j < 32; ++j) {
                 const float4 lj = light[j];
-                const double d[3] = {double(lj.x) - double(o.position[0]), double(lj.y) - double(o.position[1]),
-                                     double(lj.z) - double(o.position[2])};
-                bool in = true;
-                for (int r = 0; r < 3; ++r) {
-                    const double lp = R[r][0] * d[0] + R[r][1] * d[1] + R[r][2] * d[2];  // the inverse rotation
-                    const double m =
-                        0.05 + 1e-4 * (fabs(double(o.box_mins[r])) + fabs(double(o.box_maxs[r])) + fabs(lp));
-                    in = in && isfinite(lp) && double(o.box_mins[r]) + m < lp && lp < double(o.box_maxs[r]) - m;
-                }
-                if (in) inside |= 1u << j;
+                const float lp[3] = {lj.x, lj.y, lj.z};
+                if (light_inside_box(o, R, lp)) inside |= 1u << j;
             }
             boxes[b].light_inside = inside;
-            if (b < n_mask_boxes) {
-                // the bounding sphere that carries the box's mask bit (build_scene)
-                double c[3], h2 = 0.0;
-                for (int r = 0; r < 3; ++r) {
-                    c[r] = 0.5 * (double(o.box_mins[r]) + double(o.box_maxs[r]));
-                    const double e = 0.5 * (double(o.box_maxs[r]) - double(o.box_mins[r]));
-                    h2 += e * e;
-                }
-                double w[3];
-                for (int r = 0; r < 3; ++r)
-                    w[r] = R[0][r] * c[0] + R[1][r] * c[1] + R[2][r] * c[2] + double(o.position[r]);
-                const double wl = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-                const double rad = sqrt(h2) * 1.001 + 1e-3 * (1.0 + wl);
-                bsph[b] = make_float4(static_cast<float>(w[0]), static_cast<float>(w[1]), static_cast<float>(w[2]),
-                                      isfinite(rad) ? static_cast<float>(rad * (1.0 + 1e-6)) : HUGE_VALF);
-            }
+            if (b < n_mask_boxes) bsph[b] = box_ball(o, R);
         }
         if (kSpheres)
             for (int i = tid - kHalf; i < n_ms; i += kHalf) {
@@ -200,33 +134,13 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
 
     // ---- 2. planes and cones ---------------------------------------------
     if (p.off_bplane >= 0) {
-        // per (box, light) the face plane with the light farthest beyond it,
-        // in the float32 transform just stored (build_scene, "Round 6")
+        // per (box, light) the separating plane, in the float32 transform just stored
         float4 *bplane = reinterpret_cast<float4 *>(blob + static_cast<size_t>(p.off_bplane) * 16);
         const bool finite = T.finite && !*bad;
         for (int i = tid; i < nb * nl; i += kAnimThreads) {
-            const int b = i / nl, j = i % nl;
-            const BoxRec &B = boxes[b];
-            const float4 lj = light[j];
-            const double Lp[3] = {lj.x, lj.y, lj.z};
-            double best = -HUGE_VAL, bn[3] = {0, 0, 0}, bw = 0, bm = 0;
-            for (int a = 0; a < 3 && finite; ++a)
-                for (int sgn = -1; sgn <= 1; sgn += 2) {
-                    const double face = sgn > 0 ? B.maxs[a] : B.mins[a];
-                    const double r[4] = {B.w2l[4 * a], B.w2l[4 * a + 1], B.w2l[4 * a + 2], B.w2l[4 * a + 3]};
-                    const double sl = sgn * (r[0] * Lp[0] + r[1] * Lp[1] + r[2] * Lp[2] + r[3] - face);
-                    if (sl > best) {
-                        best = sl;
-                        for (int k = 0; k < 3; ++k) bn[k] = sgn * r[k];
-                        bw = sgn * (r[3] - face);
-                        bm = 1e-3 + 1e-5 * (T.extent + fabs(r[3]) + fabs(face));
-                    }
-                }
-            float4 out = make_float4(0.0f, 0.0f, 0.0f, -HUGE_VALF);
-            if (finite && isfinite(best) && isfinite(bw) && best > 0.01 + 2.0 * bm)
-                out = make_float4(static_cast<float>(bn[0]), static_cast<float>(bn[1]), static_cast<float>(bn[2]),
-                                  static_cast<float>(bw - bm));
-            bplane[i] = out;
+            const float4 lj = light[i % nl];
+            const float lp[3] = {lj.x, lj.y, lj.z};
+            bplane[i] = finite ? box_light_plane(boxes[i / nl], lp, T.extent) : no_plane();
         }
     }
     for (int i = tid; i < n_balls * nl; i += kAnimThreads) {
@@ -238,7 +152,7 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
         const float ball[4] = {s.x, s.y, s.z, s.w}, lp[3] = {lj.x, lj.y, lj.z};
         int bit = T.n_spheres + b;
         if (kSpheres && b >= n_mask_boxes) bit = msph[b - n_mask_boxes].slot;
-        cones[b * T.n_live + li] = anim_mask_cone(ball, lp, bit);
+        cones[b * T.n_live + li] = mask_cone(ball, lp, bit);
     }
     if (kSpheres && n_ms > 0) {
         // the BVH's bounds, node by node, from the spheres' boxes
@@ -259,7 +173,7 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
                 const int slot = msph[i / nl].slot, j = i % nl;
                 const float4 lj = light[j];
                 const float lp[3] = {lj.x, lj.y, lj.z};
-                scone[j * T.n_spheres + slot] = anim_shadow_cone(sph[slot], smeta[slot].radius, lp);
+                scone[j * T.n_spheres + slot] = shadow_cone(sph[slot], smeta[slot].radius, lp);
             }
         }
     }
@@ -277,7 +191,7 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
         uint64_t bits = 0;
         for (int b = 0; b < n_balls; ++b) {
             const MaskCone &c = cones[b * T.n_live + li];
-            if (anim_texel_hit(w, c)) bits |= uint64_t{1} << c.bit;
+            if (texel_hit(w, w[3], w[4], c)) bits |= uint64_t{1} << c.bit;
         }
         if (T.dmask_bytes == 2)
             reinterpret_cast<uint16_t *>(dmask)[i] =
@@ -294,7 +208,7 @@ __global__ __launch_bounds__(kAnimThreads) void animate_kernel(const AnimParams 
 
 size_t animate_lds(const AnimTable &t) {
     const int n = anim_mask_balls(t);
-    return lds_boxes_at(n, t.n_live) + (t.n_msph > 0 ? static_cast<size_t>(t.n_spheres) * sizeof(AnimSphereBox) : 0);
+    return lds_boxes_at(n, t.n_live) + (t.n_msph > 0 ? static_cast<size_t>(t.n_spheres) * sizeof(SphereBox) : 0);
 }
 
 hipError_t launch_animate(const AnimParams &p, bool spheres, int n_frames, size_t lds, hipStream_t stream) {

@@ -496,19 +496,12 @@ void build_bvh(std::vector<SphereRec> &sph, std::vector<SphereMeta> &smeta, std:
         const double c[3] = {sph[i].cx, sph[i].cy, sph[i].cz};
         const double r = std::sqrt(static_cast<double>(sph[i].rr));  // |radius| as the test sees it
         bool ok = std::isfinite(r);
-        double mag = 0.0;
+        const SphereBox box = sphere_box(sph[i], r, extent);
         for (int a = 0; a < 3; ++a) {
             ok = ok && std::isfinite(c[a]);
-            mag = std::max(mag, std::fabs(c[a]) + r);
-        }
-        // the kernel's node test (rt_kernel.hip, node_hit) has no slack of
-        // its own: its error, ~2^-22 (|x| + |o|) / |d|, stays far below this
-        // margin for every box coordinate x and ray origin o of the scene
-        const double margin = 1e-3 + 1e-4 * std::max(mag, extent);
-        for (int a = 0; a < 3; ++a) {
             it.c[a] = c[a];
-            it.lo[a] = c[a] - r - margin;
-            it.hi[a] = c[a] + r + margin;
+            it.lo[a] = box.lo[a];
+            it.hi[a] = box.hi[a];
         }
         (ok ? finite : other).push_back(it);
     }
@@ -812,13 +805,9 @@ const MaskCones &mask_cones(int n) {
 
 // Build the device blob: [spheres][sphere meta][boxes][materials][lights]
 // [light x material products]; every section 16-B aligned.
-// Shadow direction masks (rt_internal.h, kMaskMaxSpheres): float64 geometry.
-// A shadow ray from shaded point p runs from p + 0.01 n towards the light L
-// (:808-809): within 0.01 of the segment [L, p], i.e. of the ray from L in
-// the direction of p - L. Sphere s (centre c, radius r, d = |c - L|) can
-// block it only if that ray passes within rp = r + 0.021 + 1e-3 d of c (the
-// ShadowCone inflation): its direction within asin(rp / d) of (c - L) / d,
-// or any direction when d <= rp. A texel is the spherical image of a square
+// Shadow direction masks (rt_internal.h, kMaskMaxSpheres): float64 geometry,
+// the cone of each sphere from the light and the texel test of rt_cull.h
+// (mask_cone, texel_hit). A texel is the spherical image of a square
 // of the cube face; it lies inside the cone around its centre direction
 // whose half-angle is the largest angle to its four corners (a cone narrower
 // than 90 degrees is convex, so holding the corners it holds the square).
@@ -834,45 +823,31 @@ static void build_direction_masks(const std::vector<SphereRec> &sph, const std::
     out.clear();
     for (int j = 0; j < n_lights; ++j) {
         if (lrec[j].dead != 0.0f) continue;
-        // each sphere's cone from this light: axis, half-angle (or everywhere);
-        // the texel test angle(w, axis) <= alpha + half + 1e-3 is evaluated on
-        // cosines, dot(w, axis) >= cos(alpha + half + 1e-3) (both angles are
-        // below pi; acos is decreasing), with cos / sin of half + 1e-3 per
-        // sphere and of alpha per texel: no inverse cosine per (texel, sphere)
-        std::vector<double> ax(3 * sph.size()), half(sph.size()), ch(sph.size()), sh(sph.size());
-        std::vector<char> every(sph.size(), 0);
+        // each sphere's cone from this light (rt_cull.h), with cos / sin of
+        // half + 1e-3 per sphere and of alpha per texel: no inverse cosine per
+        // (texel, sphere)
+        std::vector<MaskCone> cone(sph.size());
+        std::vector<double> half(sph.size());
         for (size_t s = 0; s < sph.size(); ++s) {
-            double v[3] = {double(sph[s].cx) - lights[j].position[0], double(sph[s].cy) - lights[j].position[1],
-                           double(sph[s].cz) - lights[j].position[2]};
-            const double d = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-            const double rp = double(smeta[s].radius) + 0.021 + 1e-3 * d;
-            if (!(std::isfinite(d) && std::isfinite(rp)) || d <= rp) {
-                every[s] = 1;
-                continue;
-            }
-            for (int k = 0; k < 3; ++k) ax[3 * s + k] = v[k] / d;
-            half[s] = std::asin(std::min(1.0, rp / d));
-            ch[s] = std::cos(half[s] + 1e-3);
-            sh[s] = std::sin(half[s] + 1e-3);
+            const float ball[4] = {sph[s].cx, sph[s].cy, sph[s].cz, smeta[s].radius};
+            cone[s] = mask_cone(ball, lights[j].position, static_cast<int>(s), &half[s]);
         }
         const size_t base = out.size();
         out.resize(base + static_cast<size_t>(6) * n * n * words, 0u);
         for (const MaskCones::Block &bl : mc.blocks)
             for (size_t s = 0; s < sph.size(); ++s) {
-                if (!every[s]) {
+                const MaskCone &c = cone[s];
+                if (!c.every) {
                     // cos(reach + half + 1e-3), less a margin for rounding
-                    const double lim = bl.cr * ch[s] - bl.sr * sh[s] - 1e-9;
-                    const double c = bl.w[0] * ax[3 * s] + bl.w[1] * ax[3 * s + 1] + bl.w[2] * ax[3 * s + 2];
-                    if (bl.reach + half[s] + 1e-3 < 3.141592653589793 && c < lim) continue;
+                    const double lim = bl.cr * c.ch - bl.sr * c.sh - 1e-9;
+                    const double dot = bl.w[0] * c.ax[0] + bl.w[1] * c.ax[1] + bl.w[2] * c.ax[2];
+                    if (bl.reach + half[s] + 1e-3 < 3.141592653589793 && dot < lim) continue;
                 }
                 for (int row = bl.r0; row < bl.r1; ++row)
                     for (int col = bl.c0; col < bl.c1; ++col) {
                         const size_t t = (static_cast<size_t>(bl.face) * n + row) * n + col;
-                        const double *w = &mc.w[3 * t];
-                        // cos(alpha + half + 1e-3), less 1e-12 for rounding (far below the 1e-3 rad margin)
-                        const double lim = mc.ca[t] * ch[s] - mc.sa[t] * sh[s] - 1e-12;
-                        const double c = w[0] * ax[3 * s] + w[1] * ax[3 * s + 1] + w[2] * ax[3 * s + 2];
-                        if (every[s] || c >= lim) out[base + t * words + s / 64] |= uint64_t{1} << (s % 64);
+                        if (texel_hit(&mc.w[3 * t], mc.ca[t], mc.sa[t], c))
+                            out[base + t * words + s / 64] |= uint64_t{1} << (s % 64);
                     }
             }
     }
@@ -1114,6 +1089,7 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     std::vector<SphereRec> sph;
     std::vector<SphereMeta> smeta;
     std::vector<BoxRec> boxes;
+    std::vector<float4> ball;  // the boxes' bounding balls (mask bits)
     for (int i = 0; i < n_objs; ++i) {
         const rt_object &o = objs[i];
         const int kind = object_kind(o);
@@ -1128,44 +1104,17 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
             // is a sphere of radius |r|: the test only sees r*r, :588)
             smeta.push_back({i, o.material, std::fabs(o.radius), 0});
         } else {
-            // the transforms as the reference's GL evaluates them per ray (rt_camera.cpp)
-            float L[16], W[16], N[9];
-            reference_box_transforms(o.position, o.angles, L, W, N);
+            // the record and the culling terms, as the animate kernel derives them (rt_cull.h)
             BoxRec b{};
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 4; ++c) {  // stored row-major
-                    b.w2l[r * 4 + c] = W[c * 4 + r];
-                    b.l2w[r * 4 + c] = L[c * 4 + r];
-                }
-            // the normal matrix transpose(inverse(mat3(L))), stored row-major
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) b.nrm[r * 3 + c] = N[c * 3 + r];
-            std::memcpy(b.mins, o.box_mins, 12);
-            std::memcpy(b.maxs, o.box_maxs, 12);
+            box_record(o, b);
             b.obj_index = i;
             b.material = o.material;
-            for (int r = 0; r < 3; ++r) b.w2l_w0[r] = b.w2l[r * 4 + 3] * 0.0f;  // the kernel adds it as is
-            b.translate_only = 1;
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c)
-                    if (b.w2l[r * 4 + c] != (r == c ? 1.0f : 0.0f)) b.translate_only = 0;
-            // Lights strictly inside the box by a margin (float64): a shadow
-            // segment that starts inside the box then ends inside it too (its
-            // end is the light + 0.01 n, :808-809), so the box cannot occlude.
-            const M4 Wd = inverse(transform(o.position, o.angles));  // culling only (float64)
-            for (int j = 0; j < n_lights && j < 32; ++j) {
-                double lp[3];
-                bool in = true;
-                for (int r = 0; r < 3; ++r) {
-                    lp[r] = Wd.m[0][r] * lights[j].position[0] + Wd.m[1][r] * lights[j].position[1] +
-                            Wd.m[2][r] * lights[j].position[2] + Wd.m[3][r];
-                    const double m = 0.05 + 1e-4 * (std::fabs(o.box_mins[r]) + std::fabs(o.box_maxs[r]) +
-                                                    std::fabs(lp[r]));
-                    in = in && std::isfinite(lp[r]) && o.box_mins[r] + m < lp[r] && lp[r] < o.box_maxs[r] - m;
-                }
-                if (in) b.light_inside |= 1u << j;
-            }
+            double R[3][3];
+            rotation64(o.angles, R);
+            for (int j = 0; j < n_lights && j < 32; ++j)
+                if (light_inside_box(o, R, lights[j].position)) b.light_inside |= 1u << j;
             boxes.push_back(b);
+            ball.push_back(box_ball(o, R));
         }
     }
     // |coordinate| bound of the finite objects (BVH margins); an animated
@@ -1211,26 +1160,11 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
         }
         for (int j = 0; j < n_lights; ++j) lm[m * n_lights + j].always = tame ? 0 : 1;
     }
-    // Shadow culling cones of every (light, sphere) pair (float64; culling
-    // only, the margins dwarf the float32 rounding of the stored values).
+    // Shadow culling cones of every (light, sphere) pair (rt_cull.h).
     std::vector<ShadowCone> cones(static_cast<size_t>(n_lights) * sph.size());
     for (int j = 0; j < n_lights; ++j)
-        for (size_t s = 0; s < sph.size(); ++s) {
-            ShadowCone &c = cones[j * sph.size() + s];
-            const double v[3] = {double(sph[s].cx) - lights[j].position[0], double(sph[s].cy) - lights[j].position[1],
-                                 double(sph[s].cz) - lights[j].position[2]};
-            const double d = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-            const double rp = double(smeta[s].radius) + 0.021 + 1e-3 * d;
-            if (!(std::isfinite(d) && std::isfinite(rp)) || d <= rp) {
-                c.near = 1.0f;  // always a candidate
-                continue;
-            }
-            for (int r = 0; r < 3; ++r) c.v[r] = static_cast<float>(v[r] / d);
-            c.far = static_cast<float>(d - rp);
-            const double sp = rp / d;
-            c.sph = static_cast<float>(sp);
-            c.cph = static_cast<float>(std::sqrt(std::max(0.0, 1.0 - sp * sp)));
-        }
+        for (size_t s = 0; s < sph.size(); ++s)
+            cones[j * sph.size() + s] = shadow_cone(sph[s], smeta[s].radius, lights[j].position);
     // A light with zero diffuse and specular colour (the reference's ambient
     // light, :202-207) adds +-0 to the sums for every finite material with
     // shininess >= 0 (pow then stays finite), so lit and shadowed agree and
@@ -1258,16 +1192,7 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     lay.off_lights = off;  off += units(lrec.size() * sizeof(LightRec));
     lay.off_lightmat = off; off += units(lm.size() * sizeof(LightMatRec));
     // Round 6: in a scene of several boxes (chosen by the object kinds alone,
-    // as the mask bits), per (box, light) the face plane of the box (in the
-    // float32 transform the kernel uses) with the light farthest beyond it:
-    // a shadow segment whose start lies beyond that plane too cannot be
-    // occluded by the box (both of its ends beyond the plane of a face; the
-    // exact slab test then sees that axis' entry at t > 1 or a miss). Stored
-    // as (n, w) with the margin m folded into w (a start counts as beyond
-    // when n . start + w > 0), m = 1e-3 + 1e-5 (scene extent + |w|), far
-    // above the float32 rounding of n . start and of the kernel's transform;
-    // kept only if the light lies beyond by more than 0.01 (the segment ends
-    // at L + 0.01 n, :808-809) + 2 m; else w = -inf (never beyond).
+    // as the mask bits), per (box, light) the separating plane (rt_cull.h).
     std::vector<float4> bplane;
     lay.off_bplane = -1;
     if (boxes.size() >= 2) {
@@ -1276,29 +1201,10 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
             for (int k = 0; k < 3; ++k)
                 finite = finite && std::isfinite(objs[i].position[k]) && std::isfinite(objs[i].box_mins[k]) &&
                          std::isfinite(objs[i].box_maxs[k]) && std::isfinite(objs[i].radius);
-        bplane.assign(boxes.size() * static_cast<size_t>(n_lights), float4{0.0f, 0.0f, 0.0f, -HUGE_VALF});
-        for (size_t b = 0; b < boxes.size() && finite; ++b) {
-            const BoxRec &B = boxes[b];
-            for (int j = 0; j < n_lights; ++j) {
-                const double L[3] = {lights[j].position[0], lights[j].position[1], lights[j].position[2]};
-                double best = -HUGE_VAL, bn[3] = {0, 0, 0}, bw = 0, bm = 0;
-                for (int a = 0; a < 3; ++a)
-                    for (int sgn = -1; sgn <= 1; sgn += 2) {
-                        const double face = sgn > 0 ? B.maxs[a] : B.mins[a];
-                        const double r[4] = {B.w2l[4 * a], B.w2l[4 * a + 1], B.w2l[4 * a + 2], B.w2l[4 * a + 3]};
-                        const double sl = sgn * (r[0] * L[0] + r[1] * L[1] + r[2] * L[2] + r[3] - face);
-                        if (sl > best) {
-                            best = sl;
-                            for (int k = 0; k < 3; ++k) bn[k] = sgn * r[k];
-                            bw = sgn * (r[3] - face);
-                            bm = 1e-3 + 1e-5 * (extent + std::fabs(r[3]) + std::fabs(face));
-                        }
-                    }
-                if (std::isfinite(best) && std::isfinite(bw) && best > 0.01 + 2.0 * bm)
-                    bplane[b * n_lights + j] = float4{static_cast<float>(bn[0]), static_cast<float>(bn[1]),
-                                                      static_cast<float>(bn[2]), static_cast<float>(bw - bm)};
-            }
-        }
+        bplane.assign(boxes.size() * static_cast<size_t>(n_lights), no_plane());
+        for (size_t b = 0; b < boxes.size() && finite; ++b)
+            for (int j = 0; j < n_lights; ++j)
+                bplane[b * n_lights + j] = box_light_plane(boxes[b], lights[j].position, extent);
         lay.off_bplane = off;
         off += units(bplane.size() * sizeof(float4));
     }
@@ -1316,11 +1222,7 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     lay.off_dmask = -1;
     lay.dmask_n = 0;
     // Round 6: in a scene of several boxes the boxes get mask bits too (bit
-    // n_spheres + b), from their bounding spheres. A box that can occlude a
-    // shadow segment holds a point of it, and so does its bounding sphere: the
-    // spheres' cone test is conservative for it. The sphere's radius carries
-    // 1e-3 relative + 1e-3 (1 + |centre|) of margin over the float64 half
-    // diagonal, far above the float32 transforms' error. The choice depends
+    // n_spheres + b), from their bounding balls (rt_cull.h). The choice depends
     // on the object kinds alone (the blob layout rt_render_batch_scenes
     // requires to be shared by the frames of an animated scene): a one-box
     // scene — the room of configs 2-5 — keeps its box's shortcuts instead.
@@ -1347,25 +1249,9 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
         if (box_bits) {
             std::vector<SphereRec> bsph(sph);
             std::vector<SphereMeta> bmeta(smeta);
-            for (int i = 0; i < n_objs; ++i) {
-                const rt_object &o = objs[i];
-                if (object_kind(o) != 1) continue;
-                const M4 T = transform(o.position, o.angles);
-                double c[3], h2 = 0.0;
-                for (int r = 0; r < 3; ++r) {
-                    const double lc = 0.5 * (double(o.box_mins[r]) + double(o.box_maxs[r]));
-                    const double e = 0.5 * (double(o.box_maxs[r]) - double(o.box_mins[r]));
-                    h2 += e * e;
-                    c[r] = lc;
-                }
-                double w[3];
-                for (int r = 0; r < 3; ++r) w[r] = T.m[0][r] * c[0] + T.m[1][r] * c[1] + T.m[2][r] * c[2] + T.m[3][r];
-                const double wl = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-                const double rad = std::sqrt(h2) * 1.001 + 1e-3 * (1.0 + wl);
-                bsph.push_back({static_cast<float>(w[0]), static_cast<float>(w[1]), static_cast<float>(w[2]), 0.0f});
-                // (a non-finite box: a non-finite radius, the bit set everywhere)
-                bmeta.push_back({i, o.material, std::isfinite(rad) ? static_cast<float>(rad * (1.0 + 1e-6))
-                                                                   : HUGE_VALF, 0});
+            for (size_t b = 0; b < boxes.size(); ++b) {
+                bsph.push_back({ball[b].x, ball[b].y, ball[b].z, 0.0f});
+                bmeta.push_back({boxes[b].obj_index, boxes[b].material, ball[b].w, 0});
             }
             build_direction_masks(bsph, bmeta, lights, lrec, lay.dmask_n, dmask);
             lay.dmask_box = 1;
@@ -1424,11 +1310,10 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
             const rt_light &L = lights[live[k]];
             std::vector<double> key(sph.size());
             for (size_t q = 0; q < sph.size(); ++q) {
-                const double v[3] = {double(sph[q].cx) - L.position[0], double(sph[q].cy) - L.position[1],
-                                     double(sph[q].cz) - L.position[2]};
-                const double d = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-                const double r = double(smeta[q].radius);
-                key[q] = (std::isfinite(d) && std::isfinite(r) && d > r + 0.021 + 1e-3 * d) ? r / d : HUGE_VAL;
+                const float c[3] = {sph[q].cx, sph[q].cy, sph[q].cz};
+                double v[3], d, rp;
+                key[q] = ball_from_light(c, smeta[q].radius, L.position, v, d, rp) ? double(smeta[q].radius) / d
+                                                                                    : HUGE_VAL;
             }
             std::vector<int> order(sph.size());
             for (size_t q = 0; q < sph.size(); ++q) order[q] = static_cast<int>(q);
@@ -1751,6 +1636,61 @@ int anim_plan(const char *who_c, const rt_object *base, const rt_object_anim *an
     return RT_OK;
 }
 
+// Phase 3 of the animate kernel for one (ball, live light li): the cone's bit
+// ORed into the light's masks, texel by texel.
+static void or_cone_bits(const AnimPlan &plan, std::vector<float4> &blob, int li, const MaskCone &c) {
+    const AnimTable &T = plan.tab;
+    const size_t texels = static_cast<size_t>(6) * T.dmask_n * T.dmask_n;
+    const double *w = reinterpret_cast<const double *>(plan.table.data() + T.off_cone);
+    unsigned char *dmask = reinterpret_cast<unsigned char *>(blob.data() + plan.ds.layout.off_dmask);
+    for (size_t t = 0; t < texels; ++t) {
+        if (!texel_hit(w + 5 * t, w[5 * t + 3], w[5 * t + 4], c)) continue;
+        unsigned char *m = dmask + (static_cast<size_t>(li) * texels + t) * T.dmask_bytes;
+        uint64_t v = 0;
+        std::memcpy(&v, m, T.dmask_bytes);
+        v |= uint64_t{1} << c.bit;
+        std::memcpy(m, &v, T.dmask_bytes);
+    }
+}
+
+void anim_apply_boxes_host(const AnimPlan &plan, float time, std::vector<float4> &blob) {
+    const AnimTable &T = plan.tab;
+    const SceneLayout &L = plan.ds.layout;
+    const unsigned char *table = plan.table.data();
+    const rt_object *base = reinterpret_cast<const rt_object *>(table + T.off_base);
+    const rt_object_anim *anim = reinterpret_cast<const rt_object_anim *>(table + T.off_anim);
+    const float4 *light = reinterpret_cast<const float4 *>(table + T.off_light);
+    BoxRec *boxes = reinterpret_cast<BoxRec *>(blob.data() + L.off_boxes);
+    const int nb = T.n_boxes, nl = T.n_lights, n_mask_boxes = anim_mask_boxes(T);
+    // 1. records, light_inside and balls
+    std::vector<float4> ball(n_mask_boxes);
+    bool finite = T.finite != 0;
+    for (int b = 0; b < nb; ++b) {
+        const rt_object o = animate_object(base[b], anim[b], time);
+        box_record(o, boxes[b]);
+        for (int r = 0; r < 3; ++r)
+            finite = finite && std::isfinite(o.position[r]) && std::isfinite(o.box_mins[r]) &&
+                     std::isfinite(o.box_maxs[r]);
+        double R[3][3];
+        rotation64(o.angles, R);
+        uint32_t inside = 0;
+        for (int j = 0; j < nl && j < 32; ++j)
+            if (light_inside_box(o, R, &light[j].x)) inside |= 1u << j;
+        boxes[b].light_inside = inside;
+        if (b < n_mask_boxes) ball[b] = box_ball(o, R);
+    }
+    // 2. the separating planes; 3. the boxes' mask bits
+    float4 *bplane = L.off_bplane >= 0 ? blob.data() + L.off_bplane : nullptr;
+    for (int i = 0; bplane && i < nb * nl; ++i)
+        bplane[i] = finite ? box_light_plane(boxes[i / nl], &light[i % nl].x, T.extent) : no_plane();
+    for (int i = 0; i < n_mask_boxes * nl; ++i) {
+        const int b = i / nl, j = i % nl;
+        int32_t li;
+        std::memcpy(&li, &light[j].w, 4);
+        if (li >= 0) or_cone_bits(plan, blob, li, mask_cone(&ball[b].x, &light[j].x, T.n_spheres + b));
+    }
+}
+
 void anim_apply_spheres_host(const AnimPlan &plan, float time, std::vector<float4> &blob) {
     const AnimTable &T = plan.tab;
     if (T.n_msph == 0) return;
@@ -1768,7 +1708,7 @@ void anim_apply_spheres_host(const AnimPlan &plan, float time, std::vector<float
     // 2. the BVH's bounds and the ShadowCone entries
     const AnimNodeRange *range = reinterpret_cast<const AnimNodeRange *>(table + T.off_node);
     BvhNode *bvh = reinterpret_cast<BvhNode *>(blob.data() + T.blob_bvh);
-    std::vector<AnimSphereBox> sbox(T.n_spheres);
+    std::vector<SphereBox> sbox(T.n_spheres);
     for (int s = 0; s < T.n_spheres; ++s) sbox[s] = anim_sphere_box(sph[s], smeta[s].radius, T.extent);
     for (int n = 0; n < T.n_bvh; ++n) anim_node_bounds(sbox.data(), range[n], bvh[n].lo, bvh[n].hi);
     if (T.blob_cone >= 0) {
@@ -1776,32 +1716,19 @@ void anim_apply_spheres_host(const AnimPlan &plan, float time, std::vector<float
         for (int i = 0; i < T.n_msph; ++i)
             for (int j = 0; j < T.n_lights; ++j) {
                 const int slot = msph[i].slot;
-                const float lp[3] = {light[j].x, light[j].y, light[j].z};
-                scone[j * T.n_spheres + slot] = anim_shadow_cone(sph[slot], smeta[slot].radius, lp);
+                scone[j * T.n_spheres + slot] = shadow_cone(sph[slot], smeta[slot].radius, &light[j].x);
             }
     }
     // 3. the moving spheres' mask bits
     if (T.dmask_n <= 0) return;
-    const size_t texels = static_cast<size_t>(6) * T.dmask_n * T.dmask_n;
-    const double *cone_tab = reinterpret_cast<const double *>(table + T.off_cone);
-    unsigned char *dmask = reinterpret_cast<unsigned char *>(blob.data() + plan.ds.layout.off_dmask);
     for (int j = 0; j < T.n_lights; ++j) {
         int32_t li;
         std::memcpy(&li, &light[j].w, 4);
         if (li < 0) continue;
-        const float lp[3] = {light[j].x, light[j].y, light[j].z};
         for (int i = 0; i < T.n_msph; ++i) {
             const SphereRec &s = sph[msph[i].slot];
             const float ball[4] = {s.cx, s.cy, s.cz, smeta[msph[i].slot].radius};
-            const MaskCone c = anim_mask_cone(ball, lp, msph[i].slot);
-            for (size_t t = 0; t < texels; ++t) {
-                if (!anim_texel_hit(cone_tab + 5 * t, c)) continue;
-                unsigned char *m = dmask + (static_cast<size_t>(li) * texels + t) * T.dmask_bytes;
-                uint64_t v = 0;
-                std::memcpy(&v, m, T.dmask_bytes);
-                v |= uint64_t{1} << c.bit;
-                std::memcpy(m, &v, T.dmask_bytes);
-            }
+            or_cone_bits(plan, blob, li, mask_cone(ball, &light[j].x, msph[i].slot));
         }
     }
 }
@@ -1823,56 +1750,26 @@ int rt_debug_anim_validate(const rt_object *base, const rt_object_anim *anim, co
 
 // Development hook (host only, not part of include/rt.h): the slot blob of
 // rt_anim_create2's scene at `time` as the host makes it (rt_debug_anim_blob's
-// layout). The spheres' parts — records, BVH bounds, ShadowCone entries, mask
-// bits — come from the animate kernel's own functions (rt_anim.h) applied to
-// the template; the boxes' records, planes and mask bits are build_scene's of
-// the objects at `time`. meta (24 ints): rt_debug_scene_blob's. Returns the
-// blob's bytes (copied when they fit in cap), or a negative RT_ERR_*.
+// layout): the animate kernel's phases in plain loops over the plan's table
+// (anim_apply_boxes_host, anim_apply_spheres_host; the arithmetic is the
+// kernel's own text, rt_cull.h and rt_anim.h) applied to the template. meta
+// (24 ints): rt_debug_scene_blob's. Returns the blob's bytes (copied when
+// they fit in cap), or a negative RT_ERR_*.
 long long rt_debug_anim_host_blob(const rt_object *base, const rt_object_anim *anim, const rt_anim_channel *radius,
                                   int n_objs, const rt_material *mats, int n_mats, const rt_light *lights,
                                   int n_lights, float time, void *out, long long cap, int32_t *meta) {
     AnimPlan plan;
-    int rc = anim_plan("rt_anim_create2", base, anim, radius, n_objs, mats, n_mats, lights, n_lights, 1, true, plan);
+    const int rc =
+        anim_plan("rt_anim_create2", base, anim, radius, n_objs, mats, n_mats, lights, n_lights, 1, true, plan);
     if (rc != RT_OK) return rc;
     if (plan.time_bound && !(std::fabs(time) <= kAnimTimeBound)) {
         set_error("rt_debug_anim_host_blob: time outside the scene's range");
         return RT_ERR_UNSUPPORTED;
     }
     std::vector<float4> blob = plan.blob;
+    anim_apply_boxes_host(plan, time, blob);
     anim_apply_spheres_host(plan, time, blob);
     const SceneLayout &L = plan.ds.layout;
-    if (plan.tab.n_boxes > 0) {
-        std::vector<rt_object> objs(n_objs);
-        if ((rc = rt_animate_objects2(base, anim, radius, n_objs, time, objs.data())) != RT_OK) return rc;
-        // (a sphere keeps its base's kind here: its radius at `time` plays no part in the boxes' data)
-        for (int i = 0; i < n_objs; ++i)
-            if (object_kind(base[i]) != 1) objs[i] = base[i];
-        std::vector<float4> at;
-        DeviceScene ds;
-        if ((rc = build_scene(objs.data(), n_objs, mats, n_mats, lights, n_lights, at, ds, true, plan.tab.extent)) != RT_OK)
-            return rc;
-        if (std::memcmp(&ds.layout, &L, sizeof L) != 0) {
-            set_error("rt_debug_anim_host_blob: the boxes at this time change the layout");
-            return RT_ERR_UNSUPPORTED;
-        }
-        std::memcpy(blob.data() + L.off_boxes, at.data() + L.off_boxes, static_cast<size_t>(L.n_boxes) * sizeof(BoxRec));
-        if (L.off_bplane >= 0)
-            std::memcpy(blob.data() + L.off_bplane, at.data() + L.off_bplane,
-                        static_cast<size_t>(L.n_boxes) * L.n_lights * sizeof(float4));
-        if (L.dmask_box) {
-            const size_t n = static_cast<size_t>(plan.tab.n_live) * 6 * L.dmask_n * L.dmask_n;
-            unsigned char *m = reinterpret_cast<unsigned char *>(blob.data() + L.off_dmask);
-            const unsigned char *h = reinterpret_cast<const unsigned char *>(at.data() + L.off_dmask);
-            const uint64_t box_bits = ~((uint64_t{1} << L.n_spheres) - 1u);
-            for (size_t t = 0; t < n; ++t) {
-                uint64_t v = 0, w = 0;
-                std::memcpy(&v, m + t * L.dmask_bytes, L.dmask_bytes);
-                std::memcpy(&w, h + t * L.dmask_bytes, L.dmask_bytes);
-                v |= w & box_bits;
-                std::memcpy(m + t * L.dmask_bytes, &v, L.dmask_bytes);
-            }
-        }
-    }
     const long long bytes = static_cast<long long>(blob.size() * sizeof(float4));
     if (out && cap >= bytes) std::memcpy(out, blob.data(), static_cast<size_t>(bytes));
     if (meta) {

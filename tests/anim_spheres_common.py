@@ -2,7 +2,9 @@
 blob scenes of the moving-sphere tests, a reader of the scene blob, and the
 checks (a)-(e) on a slot blob at a time — from the host hook
 (rt_debug_anim_host_blob) or from the device (rt_debug_anim_blob) — against
-the scene the host builds of rt_animate_objects2(time)."""
+the scene the host builds of rt_animate_objects2(time). And by
+test_anim_boxes_host.py and test_gpu_anim.py: the scenes of the box phases'
+tests and readers of the records and planes."""
 import ctypes as C
 
 import numpy as np
@@ -98,6 +100,109 @@ def scene_cone_table():
 
 
 BLOB_SCENES = {"room16": scene_room16, "boxes_spheres": scene_boxes_spheres, "cone_table": scene_cone_table}
+
+
+# ---- the box phases (test_anim_boxes_host.py, test_gpu_anim.py) ---------------
+BOXREC = np.dtype([("w2l", "<u4", 12), ("l2w", "<u4", 12), ("nrm", "<u4", 9), ("mins", "<u4", 3), ("maxs", "<u4", 3),
+                   ("obj_index", "<i4"), ("material", "<i4"), ("light_inside", "<u4"), ("translate_only", "<i4"),
+                   ("w2l_w0", "<u4", 3), ("pad", "<i4", 2)])
+assert BOXREC.itemsize == BOXREC_BYTES
+ON_LIGHT_TIME = 1.0  # box 0 of two_boxes and of box_spheres has its centre on a light
+BOX_TIMES = [0.0, 0.8125, -2.375, 7.3, ON_LIGHT_TIME]
+
+
+def live_lights(rng, n):
+    out = []
+    for _ in range(n):
+        lt = Light()
+        lt.position[:] = rng.uniform(-6.0, 6.0, 3)
+        lt.ambient[:] = rng.uniform(0.0, 0.2, 4)
+        lt.diffuse[:] = rng.uniform(0.2, 1.0, 4)
+        lt.specular[:] = rng.uniform(0.2, 1.0, 4)
+        out.append(lt)
+    return out
+
+
+def moving_box(rng, through=None, grow=True):
+    """(box, channels). through: the position the box's centre has at
+    ON_LIGHT_TIME, on RATE_OFFSET channels; else SIN_OFFSET positions. grow:
+    a RATE angle channel and a breathing scale."""
+    ext = rng.uniform(0.4, 1.0, 3)
+    pos = rng.uniform(-5.0, 5.0, 3)
+    an = ObjectAnim()
+    for k in range(3):
+        if through is None:
+            an.position[k] = sin_offset(rng, 1.0, pos[k])
+        else:
+            rate = np.float32(rng.uniform(0.5, 3.0))
+            at = np.float32(through[k]) - rate * np.float32(ON_LIGHT_TIME)
+            an.position[k] = AnimChannel(abi.RT_ANIM_RATE_OFFSET, 0.0, float(rate), float(at))
+    an.angles[int(rng.integers(3))] = AnimChannel(abi.RT_ANIM_RATE, 0.0, float(rng.uniform(10.0, 40.0)), 0.0)
+    if grow:
+        an.scale = sin_offset(rng, 0.3, 1.0)
+    return scenes.box(tuple(-ext), tuple(ext), tuple(pos), tuple(rng.uniform(0.0, 360.0, 3)), int(rng.integers(7))), an
+
+
+def scene_two_boxes():
+    """(iii) two moving boxes, two lights, no sphere: planes and no masks."""
+    rng = np.random.default_rng(504)
+    lights = live_lights(rng, 2)
+    boxes = [moving_box(rng, through=lights[0].position), moving_box(rng)]
+    return [b for b, _ in boxes], [a for _, a in boxes], [AnimChannel(), AnimChannel()], rt.reference_materials(), lights
+
+
+def scene_box_spheres():
+    """(iv) one moving box and 12 spheres, 4 of them moving: no planes and no
+    box bits."""
+    rng = np.random.default_rng(505)
+    lights = rt.reference_lights()
+    box, an = moving_box(rng, through=lights[1].position)
+    base, anim, radius = [box], [an], [AnimChannel()]
+    for s in range(12):
+        base.append(scenes.sphere(tuple(rng.uniform(-6.0, 6.0, 3)), float(rng.uniform(0.2, 0.9)), int(rng.integers(7))))
+        anim.append(ObjectAnim())
+        radius.append(AnimChannel())
+        if s % 3 == 0:
+            move_sphere(rng, base[-1], anim[-1])
+    return base, anim, radius, rt.reference_materials(), lights
+
+
+def scene_steady_extent():
+    """Two moving boxes without a channel that grows, two lights, and a static
+    box far out that alone sets the scene's extent at every time."""
+    rng = np.random.default_rng(506)
+    boxes = [moving_box(rng, grow=False), moving_box(rng, grow=False)]
+    far = scenes.box((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0), (30.0, -20.0, 10.0), (10.0, 20.0, 30.0), 1)
+    return ([b for b, _ in boxes] + [far], [a for _, a in boxes] + [ObjectAnim()], [AnimChannel()] * 3,
+            rt.reference_materials(), live_lights(rng, 2))
+
+
+def scene_shipped():
+    """(i) the shipped animation: the room, three moving boxes and a sphere."""
+    base, anim = rt.reference_animation()
+    return base, anim, [AnimChannel() for _ in base], rt.reference_materials(), rt.reference_lights()
+
+
+BOX_SCENES = {"shipped": scene_shipped, "boxes_spheres": scene_boxes_spheres, "two_boxes": scene_two_boxes,
+              "box_spheres": scene_box_spheres}
+
+
+def box_records(buf, meta):
+    m = meta if isinstance(meta, dict) else dict(zip(META, meta))
+    off = m["off_boxes"] * 16
+    return np.frombuffer(buf[off:off + m["n_boxes"] * BOXREC_BYTES].tobytes(), BOXREC)
+
+
+def box_planes(buf, meta):
+    """The (box, light) separating planes as uint32 [box, light, 4], or None:
+    scenes of several boxes keep them right before the BVH (SceneLayout)."""
+    m = meta if isinstance(meta, dict) else dict(zip(META, meta))
+    nb, nl = m["n_boxes"], m["n_lights"]
+    if nb < 2:
+        return None
+    off = (m["off_bvh"] - nb * nl) * 16
+    assert off >= m["off_lightmat"] * 16
+    return np.frombuffer(buf[off:off + nb * nl * 16].tobytes(), "<u4").reshape(nb, nl, 4)
 
 
 def host_scene_blob(objs, mats, lights):

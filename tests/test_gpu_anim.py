@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import openglraytracer_amd as rt
+from anim_spheres_common import BOX_SCENES, ON_LIGHT_TIME, Blob, box_planes, box_records
 from conftest import GOLDEN, dev_zeros, load_fixture, manifest, parity_stats
 from openglraytracer_amd import abi
 from openglraytracer_amd.abi import AnimChannel, Light, Material, Object, ObjectAnim
@@ -313,6 +314,47 @@ def test_edges_that_flip_host_decisions(gpu_ctx, seed):
             sc.close()
     assert flips["translate_only"] == {0, 1}, flips
     assert flips["light_inside"] == {0, 1}, flips
+
+
+def test_device_box_phases_equal_their_host_run(gpu_ctx):
+    """The slot blob the animate kernel leaves (rt_debug_anim_blob, one frame
+    per launch) against the host run of the same phases over the same table
+    (rt_debug_anim_host_blob; one text, rt_cull.h), at 3 times in 3 scenes:
+    boxes with mask bits beside moving spheres, two boxes and no sphere (planes,
+    animate_kernel<false>), one box with spheres (no planes, no box bits). The
+    records' float words, translate_only and light_inside are equal; so is the
+    plane section, bit for bit: float64 products and sums of the float32 record
+    and the lights, no contraction, no transcendental. The boxes' mask bits
+    pass through the device's double sincos (the balls): at most 1 in 100,000
+    may differ, of at least 10^4 compared."""
+    compared, differing = 0, []
+    for name in ("boxes_spheres", "two_boxes", "box_spheres"):
+        base, anim, radius, mats, lights = BOX_SCENES[name]()
+        a = rt.Anim(gpu_ctx, base, anim, materials=mats, lights=lights,
+                    radius=None if name == "two_boxes" else radius)
+        try:
+            for t in (0.8125, -2.375, ON_LIGHT_TIME):
+                hbuf, meta = rt.anim_host_blob(base, anim, radius, mats, lights, t)
+                dbuf = a.debug_blob(t)
+                assert dbuf.size == hbuf.size, (name, t)
+                dev, hook = box_records(dbuf, meta), box_records(hbuf, meta)
+                for field in BOXREC.names:
+                    assert np.array_equal(dev[field], hook[field]), (name, t, field, dev[field], hook[field])
+                dp, hp = box_planes(dbuf, meta), box_planes(hbuf, meta)
+                assert (dp is None) == (name == "box_spheres")
+                if dp is not None:
+                    assert np.array_equal(dp, hp), (name, t, np.argwhere(dp != hp)[:10])
+                    assert (dp[..., 3] != 0xFF800000).any(), (name, t, "no plane kept")
+                d, h = Blob(dbuf, meta), Blob(hbuf, meta)
+                for b in range(len(dev) if name == "boxes_spheres" else 0):
+                    bit = np.uint64(len(d.smeta) + b)
+                    x, y = (d.masks >> bit) & np.uint64(1), (h.masks >> bit) & np.uint64(1)
+                    compared += len(x)
+                    differing += [(name, t, b, int(i)) for i in np.nonzero(x != y)[0]]
+        finally:
+            a.close()
+    print("box mask bits compared %d, differing %s" % (compared, differing))
+    assert compared >= 10000 and len(differing) * 100000 <= compared, (compared, differing)
 
 
 def test_static_scene_through_the_animated_path(gpu_ctx):

@@ -109,8 +109,9 @@ int main(int argc, char **argv) {
             return 1;
         ++g_built;
     }
-    // moving spheres (rt_anim_create2's host side, the sphere phases' arithmetic
-    // of rt_anim.h on the template blob): config 2's scene with every sphere
+    // the animate kernel's phases on the host (rt_anim_create2's host side, the
+    // box and sphere phases over the kernel's table with the arithmetic of
+    // rt_cull.h and rt_anim.h): config 2's scene with every sphere
     // moving and some breathing, and the shipped scene's boxes with its sphere
     // moving (box bits beside the sphere's); then the refusals
     for (int which = 0; which < 2; ++which) {
