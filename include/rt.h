@@ -479,6 +479,14 @@ int rt_multi_last_ms(rt_multi *m, float *kernel_ms, float *gather_ms, float *ass
  * frames then run the queue loop). Other values are refused. Output is
  * identical. */
 #define RT_OPT_PERSISTENT0 10
+/* RT_OPT_FIXED_LAYOUT (default 1): a scene with LDS shadow masks whose
+ * lights, materials and boxes lie within its layout class's maxima (4 lights,
+ * 8 materials, one box or up to 4) is staged in the class's fixed layout, and
+ * its plain persistent launches (RT_OPT_PERSISTENT0) run the kernel that
+ * takes the table offsets from the class instead of reading them per tile.
+ * 0: every launch reads the offsets at run time; the scenes' blobs are the
+ * same. Output is identical. */
+#define RT_OPT_FIXED_LAYOUT 11
 /* (option 6, a tolerance tier that summed the recursion's colours forward
  * instead of mixing them on the way back up, measured even with the exact
  * walk and was removed: DESIGN.md §3.) */

@@ -322,6 +322,13 @@ class Context:
         launch's size. Output identical either way."""
         _check(lib().rt_context_set(self._h, abi.RT_OPT_PERSISTENT0, int(value)))
 
+    def set_fixed_layout(self, on):
+        """RT_OPT_FIXED_LAYOUT: a plain persistent launch of a scene staged
+        in its layout class's fixed layout runs the kernel that takes the
+        table offsets from the class (include/rt.h). Output identical either
+        way."""
+        _check(lib().rt_context_set(self._h, abi.RT_OPT_FIXED_LAYOUT, 1 if on else 0))
+
     def set_output(self, fmt):
         """RT_OPT_OUTPUT: abi.RT_OUTPUT_RGBA32F (float4 per pixel),
         abi.RT_OUTPUT_RGBA8 (the shipped GL_RGBA8 surface, 4 bytes per pixel)

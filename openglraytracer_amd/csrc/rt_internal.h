@@ -180,8 +180,28 @@ struct FrameView {
     float proj[16];    // column-major proj*view = inverse(unproj) (float64 on the host), for culling
     float origin[3];   // ray start = camera position (:391)
     int32_t cull;      // 1: exactness-preserving culling enabled (consistent pinhole view)
+    // The camera ray's terms that depend on the view and the frame size alone,
+    // from the host (fill_view) for the plain launches (camera_ray<kLaunchPlain>):
+    // every wave tile computed them again on the vector pipe, uniform as they
+    // are (no scalar float unit). The same floats as the device's:
+    //  * unproj_half[k] = unproj[8 + k] * 0.5f, one IEEE multiplication on
+    //    either side (the kernel is built without contraction);
+    //  * rcp_hw, rcp_hh = 1.0f / float(W / 2), 1.0f / float(H / 2), IEEE on the
+    //    host; the device's rcp_refined(b).r is the correctly rounded 1 / b for
+    //    every significand (tools/probes/arith_probe.hip, exhaustive), so the
+    //    same float. (Its Rcp::b, float(W / 2), is exact and stays on the device.)
+    // A frame 1 pixel wide or high has inf here; no plain launch is one.
+    float unproj_half[4];
+    float rcp_hw, rcp_hh;
     const void *blob;  // this view's scene blob (rt_render_batch_scenes); nullptr: LaunchParams::scene
 };
+static_assert(sizeof(FrameView) == 176 && offsetof(FrameView, unproj_half) % 16 == 0, "FrameView: whole 16-B units");
+// (-DRT_HOST_VIEW_TERMS=0: a timing build whose plain launches compute the
+// terms on the device, tools/ablate.sh flags)
+#ifndef RT_HOST_VIEW_TERMS
+#define RT_HOST_VIEW_TERMS 1
+#endif
+constexpr bool kHostViewTerms = RT_HOST_VIEW_TERMS != 0;
 constexpr int kMaxViews = 8;  // frames per launch (blockIdx.z) with the views in the kernel arguments
 // Larger batches (up to RT_MAX_BATCH views, depth 0-1): the views and their
 // frame constants go to a per-context device buffer (one of kBatchSlots,
@@ -269,7 +289,7 @@ struct LaunchParams {
     // (last: kernarg_probe reads the block's end)
     float4 frame_consts[kMaxFrameConsts];
 };
-static_assert(sizeof(LaunchParams) == 5776, "kernel argument block: the hidden arguments' offsets");
+static_assert(sizeof(LaunchParams) == 5968, "kernel argument block: the hidden arguments' offsets");
 static_assert(offsetof(LaunchParams, layout) % 16 == 0, "the layout's offsets: aligned scalar loads (see above)");
 static_assert(offsetof(LaunchParams, frame_consts) + sizeof(LaunchParams::frame_consts) == sizeof(LaunchParams),
               "kernarg_probe reads the last record: nothing the kernels read lies behind it");
@@ -291,6 +311,9 @@ struct LaunchHost {
     // work-groups; persistent_groups), 0 too when a view of the batch carries
     // a scene blob of its own (rt_render_batch_scenes)
     int32_t persistent0;
+    // RT_OPT_FIXED_LAYOUT: a launch of a scene in its class's fixed layout may
+    // take the kernels that read the class's offsets (kShapeFixed)
+    int32_t fixed_layout;
     int32_t n_cu;  // the compute units a resident grid is sized for; 0: tiled launches only
 };
 // Scene shapes (render_kernel<D, ..., kShape>): the scene's features that
@@ -306,6 +329,64 @@ constexpr int kShapeMaskBytes = 15;
 constexpr int kShapeMaskTexels = 12;  // the LDS masks' texels per face edge in a depth-0 shape (rt_scene.cpp picks 12 where it fits)
 constexpr int kShapeRoom = 16;
 constexpr int kShapeWide = 32;
+// kShapeFixed (with an LDS-mask shape; the persistent kernels): the staged
+// blob has its layout class's fixed layout (fixed_layout below), so the
+// kernel takes its table addresses from the class instead of reading
+// LaunchParams::layout per wave tile. Never with RT_OPT_FIXED_LAYOUT 0.
+constexpr int kShapeFixed = 64;
+// Layout classes of the LDS-mask scenes. A class is one box or several; inside
+// it the tables a depth-0 shaped kernel reads sit at offsets that are a
+// function of the class and the sphere count alone: first the tables whose
+// sizes the class fixes — the boxes (1 or kFixedMaxBoxes records), the
+// materials, the lights and the light x material records, each padded to its
+// maximum — then the spheres, their meta records and the masks (whose size
+// follows the live lights), then what the shaped kernels do not address by
+// the class (the planes, whose place tests/anim_spheres_common.py fixes right
+// before the BVH, the BVH and its links). The sphere tables are not padded to
+// the mask bits: config 2's scene with 40 spheres has 144 B to spare under
+// kMaskLdsBudget, so any padding of them (768 B to 64 spheres) would cost it
+// its 12-texel masks. Their count is read per tile anyway, so the meta
+// records and the masks sit at a class constant plus n_spheres and 2 n_spheres
+// units. For the same 144 B the maxima of the materials and lights are the
+// reference's own tables' sizes, 7 and 3: one material more is 208 B
+// (a MatRec and three LightMatRec), one light more 352 B. Rows of light x
+// material records keep n_lights records each. build_scene pads a scene that
+// is inside the maxima and whose mask texels the padding does not change
+// (kMaskLdsBudget); every other scene keeps the compact layout. The class
+// follows from the object kinds and the counts alone, so the frames of an
+// animated scene share it.
+constexpr int kFixedMaxLights = 3, kFixedMaxMats = 7, kFixedMaxBoxes = 4;
+struct FixedLayout {
+    int32_t off_boxes, off_mats, off_lights, off_lightmat, off_spheres;
+    // the meta records and the masks of a scene of n spheres
+    __host__ __device__ constexpr int32_t off_smeta(int n) const { return off_spheres + n; }
+    __host__ __device__ constexpr int32_t off_dmask(int n) const { return off_spheres + 2 * n; }
+};
+static_assert(sizeof(SphereRec) == 16 && sizeof(SphereMeta) == 16, "a unit per sphere and table");
+__host__ __device__ constexpr FixedLayout fixed_layout(bool one_box) {
+    FixedLayout f{};
+    f.off_boxes = 0;
+    f.off_mats = f.off_boxes + (one_box ? 1 : kFixedMaxBoxes) * static_cast<int>(sizeof(BoxRec) / 16);
+    f.off_lights = f.off_mats + kFixedMaxMats * static_cast<int>(sizeof(MatRec) / 16);
+    f.off_lightmat = f.off_lights + kFixedMaxLights * static_cast<int>(sizeof(LightRec) / 16);
+    f.off_spheres = f.off_lightmat + kFixedMaxMats * kFixedMaxLights * static_cast<int>(sizeof(LightMatRec) / 16);
+    return f;
+}
+// The counts of a class: one box or 2..kFixedMaxBoxes, lights and materials
+// within their maxima, spheres (and the boxes' bits) within the masks' 64 bits.
+inline bool fixed_counts(int n_spheres, int n_boxes, int n_mats, int n_lights) {
+    return n_spheres >= 1 && n_boxes >= 1 && n_boxes <= kFixedMaxBoxes && n_lights >= 1 &&
+           n_lights <= kFixedMaxLights && n_mats >= 1 && n_mats <= kFixedMaxMats &&
+           n_spheres + (n_boxes >= 2 ? n_boxes : 0) <= kMaskMaxSpheres;
+}
+// L is its class's fixed layout (the class of its own boxes).
+inline bool layout_is_fixed(const SceneLayout &L) {
+    if (L.off_dmask < 0 || !fixed_counts(L.n_spheres, L.n_boxes, L.n_mats, L.n_lights)) return false;
+    const FixedLayout f = fixed_layout(L.n_boxes == 1);
+    return L.off_boxes == f.off_boxes && L.off_mats == f.off_mats && L.off_lights == f.off_lights &&
+           L.off_lightmat == f.off_lightmat && L.off_spheres == f.off_spheres &&
+           L.off_smeta == f.off_smeta(L.n_spheres) && L.off_dmask == f.off_dmask(L.n_spheres);
+}
 int scene_shape(const SceneLayout &L, const LaunchHost &h, int max_depth);
 // Launch shapes (render_kernel<D, ..., kShape, kLaunch>, the depth-0 shaped
 // kernels without accumulation): the launch's own uniform answers as
@@ -526,6 +607,7 @@ struct rt_context {
     int scene_shapes = 1;  // RT_OPT_SCENE_SHAPES
     int launch_shapes = 1;  // RT_OPT_LAUNCH_SHAPES
     int persistent0 = 1;  // RT_OPT_PERSISTENT0
+    int fixed_layout = 1;  // RT_OPT_FIXED_LAYOUT
     // device-side view batches (> kMaxViews views): per slot a device buffer,
     // its pinned host staging and an event after the last launch that read it
     void *batch_dev[rtamd::kBatchSlots] = {};

@@ -37,6 +37,7 @@
 #include <climits>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 
 #include "rt_internal.h"
 
@@ -1815,8 +1816,17 @@ __device__ __forceinline__ Ray camera_ray(const LaunchParams &p, const FrameView
     // short division by the (uniform) W/2, H/2 >= 1 is the correctly rounded
     // one (a 1-pixel-wide or -high frame divides by 0: IEEE path)
     const float nx = static_cast<float>(x - hw) + jx, ny = static_cast<float>(y - hh) + jy;
+    // A plain launch takes the terms that depend on the view and the frame
+    // size alone from the host (FrameView::rcp_hw, rcp_hh, unproj_half: the
+    // same floats, see there) — uniform, but 2 v_rcp, 4 fma and 4 mul per wave
+    // tile on the vector pipe otherwise. (kHostViewTerms false: the A/B build
+    // that computes them here as the other launches do.)
+    constexpr bool kHostTerms = kPlain && kHostViewTerms;
     float vx, vy;
-    if (kPlain || (hw > 0 && hh > 0)) {
+    if (kHostTerms) {
+        vx = div_r(nx, Rcp{static_cast<float>(hw), V.rcp_hw});
+        vy = div_r(ny, Rcp{static_cast<float>(hh), V.rcp_hh});
+    } else if (kPlain || (hw > 0 && hh > 0)) {
         vx = div_r(nx, rcp_refined(static_cast<float>(hw)));
         vy = div_r(ny, rcp_refined(static_cast<float>(hh)));
     } else {
@@ -1826,7 +1836,7 @@ __device__ __forceinline__ Ray camera_ray(const LaunchParams &p, const FrameView
     float ws[4], we[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        ws[k] = M[k] * vx + M[4 + k] * vy + M[8 + k] * 0.5f + M[12 + k] * 1.0f;
+        ws[k] = M[k] * vx + M[4 + k] * vy + (kHostTerms ? V.unproj_half[k] : M[8 + k] * 0.5f) + M[12 + k] * 1.0f;
         we[k] = M[k] * vx + M[4 + k] * vy + M[8 + k] * 1.0f + M[12 + k] * 1.0f;
     }
     // (the same short divisions behind a per-wave range check measured
@@ -2049,21 +2059,29 @@ __device__ __forceinline__ void persistent_tile(const LaunchParams &p, float4 *l
     // same registers, same frames, but config 2 at 256 views was slower in
     // every alternating round, medians 6.266 -> 6.275 ms, 0.15 %,
     // profiles/r11a_bench_alternating.log section 3.)
+    // kShapeFixed: the blob has its layout class's offsets (rt_internal.h
+    // fixed_layout; scene_shape compared them on the host), so the tables'
+    // addresses are literals (the meta records' and the masks': a literal plus
+    // a multiple of the sphere count) and their seven offsets are not read per
+    // tile. The counts, the planes and the BVH (not walked at depth 0) stay
+    // run-time.
     const SceneLayout &L = p.layout;
+    constexpr bool kFixed = (kShape & kShapeFixed) != 0;
+    constexpr FixedLayout F = fixed_layout((kShape & kShapeRoom) != 0);
     Scene S;
-    S.sph = lds + L.off_spheres;
-    S.smeta = reinterpret_cast<const int4 *>(lds + L.off_smeta);
+    S.sph = lds + (kFixed ? F.off_spheres : L.off_spheres);
+    S.smeta = reinterpret_cast<const int4 *>(lds + (kFixed ? F.off_smeta(L.n_spheres) : L.off_smeta));
     S.sph_cam = slot;
     S.sph_px = reinterpret_cast<const int4 *>(slot + L.n_spheres);
-    S.box = reinterpret_cast<const BoxRec *>(lds + L.off_boxes);
+    S.box = reinterpret_cast<const BoxRec *>(lds + (kFixed ? F.off_boxes : L.off_boxes));
     S.box_cam = slot + 2 * L.n_spheres;
-    S.mat = reinterpret_cast<const MatRec *>(lds + L.off_mats);
-    S.light = reinterpret_cast<const LightRec *>(lds + L.off_lights);
-    S.lm = reinterpret_cast<const LightMatRec *>(lds + L.off_lightmat);
+    S.mat = reinterpret_cast<const MatRec *>(lds + (kFixed ? F.off_mats : L.off_mats));
+    S.light = reinterpret_cast<const LightRec *>(lds + (kFixed ? F.off_lights : L.off_lights));
+    S.lm = reinterpret_cast<const LightMatRec *>(lds + (kFixed ? F.off_lightmat : L.off_lightmat));
     S.bvh = lds + L.off_bvh;
     S.blink = reinterpret_cast<const uint32_t *>(lds + L.off_blink);
     S.cone = nullptr;  // (a depth-0 mask shape: render_wave_tile sets the rest of the shape)
-    S.dmask = reinterpret_cast<const char *>(lds + L.off_dmask);
+    S.dmask = reinterpret_cast<const char *>(lds + (kFixed ? F.off_dmask(L.n_spheres) : L.off_dmask));
     S.dmask_n = kShapeMaskTexels;
     S.dmask_bytes = kShape & kShapeMaskBytes;
     S.dmask_box = L.dmask_box;
@@ -2072,11 +2090,11 @@ __device__ __forceinline__ void persistent_tile(const LaunchParams &p, float4 *l
     S.gwords = 0;
     S.glist = nullptr;
     S.olist = nullptr;
-    S.cbox = (const __attribute__((address_space(4))) BoxRec *)(blob + L.off_boxes);
-    S.clight = (const __attribute__((address_space(4))) LightRec *)(blob + L.off_lights);
+    S.cbox = (const __attribute__((address_space(4))) BoxRec *)(blob + (kFixed ? F.off_boxes : L.off_boxes));
+    S.clight = (const __attribute__((address_space(4))) LightRec *)(blob + (kFixed ? F.off_lights : L.off_lights));
 #ifdef RT_UNIFORM_MAT
-    S.cmat = (const __attribute__((address_space(4))) MatRec *)(blob + L.off_mats);
-    S.clm = (const __attribute__((address_space(4))) LightMatRec *)(blob + L.off_lightmat);
+    S.cmat = (const __attribute__((address_space(4))) MatRec *)(blob + (kFixed ? F.off_mats : L.off_mats));
+    S.clm = (const __attribute__((address_space(4))) LightMatRec *)(blob + (kFixed ? F.off_lightmat : L.off_lightmat));
 #endif
     S.nbvh = 0;
     S.ns = L.n_spheres;
@@ -2454,21 +2472,29 @@ size_t persistent_lds_bytes(const LaunchParams &p) {
 // persistent_groups says so: the grid is the kernel's resident work-groups
 // (or RT_OPT_PERSISTENT0's cap), the LDS the scene and a view's records per
 // wave.
+// `fixed`: the scene's shape carried kShapeFixed; the persistent kernels are
+// instantiated with it, the tiled ones read LaunchParams::layout (which
+// describes the same blob).
 template <bool kAccum, bool kDev, int kShape>
-hipError_t launch_shaped0(LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
+hipError_t launch_shaped0(LaunchParams &p, const LaunchHost &h, hipStream_t stream, bool fixed) {
     if constexpr (!kAccum) {
         if ((launch_shape(p, h, 0) & kLaunchPlain) != 0) {
             if constexpr (kDev) {
                 constexpr int kPersistent = kLaunchPlain | kLaunchPersistent;
                 const size_t lds = persistent_lds_bytes(p);
                 if (h.persistent0 > 0 && p.sched && lds <= kMaxLds && h.n_cu > 0) {  // (else: no occupancy query)
-                    const void *fn = reinterpret_cast<const void *>(&render_kernel<0, false, true, kShape, kPersistent>);
-                    const int groups = persistent_groups(p, h, groups_per_cu(fn, lds) * h.n_cu);
-                    if (groups > 0) {
-                        hipLaunchKernelGGL((render_kernel<0, false, true, kShape, kPersistent>), dim3(groups),
-                                           dim3(kThreads), lds, stream, p);
-                        return hipGetLastError();
-                    }
+                    const auto run = [&](auto shape) {  // the work-groups launched, 0: none
+                        constexpr int kS = decltype(shape)::value;
+                        const void *fn = reinterpret_cast<const void *>(&render_kernel<0, false, true, kS, kPersistent>);
+                        const int groups = persistent_groups(p, h, groups_per_cu(fn, lds) * h.n_cu);
+                        if (groups > 0)
+                            hipLaunchKernelGGL((render_kernel<0, false, true, kS, kPersistent>), dim3(groups),
+                                               dim3(kThreads), lds, stream, p);
+                        return groups;
+                    };
+                    const int groups = fixed ? run(std::integral_constant<int, kShape | kShapeFixed>{})
+                                             : run(std::integral_constant<int, kShape>{});
+                    if (groups > 0) return hipGetLastError();
                 }
             }
             return launch_kernel<0, false, kDev, kShape, kLaunchPlain>(p, h, stream);
@@ -2478,13 +2504,15 @@ hipError_t launch_shaped0(LaunchParams &p, const LaunchHost &h, hipStream_t stre
 }
 template <bool kAccum, bool kDev>
 hipError_t launch_depth0(LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
-    switch (scene_shape(p.layout, h, 0)) {
-        case 2: return launch_shaped0<kAccum, kDev, 2>(p, h, stream);
-        case 4: return launch_shaped0<kAccum, kDev, 4>(p, h, stream);
-        case 8: return launch_shaped0<kAccum, kDev, 8>(p, h, stream);
-        case 2 | kShapeRoom: return launch_shaped0<kAccum, kDev, 2 | kShapeRoom>(p, h, stream);
-        case 4 | kShapeRoom: return launch_shaped0<kAccum, kDev, 4 | kShapeRoom>(p, h, stream);
-        case 8 | kShapeRoom: return launch_shaped0<kAccum, kDev, 8 | kShapeRoom>(p, h, stream);
+    const int shape = scene_shape(p.layout, h, 0);
+    const bool fixed = (shape & kShapeFixed) != 0;
+    switch (shape & ~kShapeFixed) {
+        case 2: return launch_shaped0<kAccum, kDev, 2>(p, h, stream, fixed);
+        case 4: return launch_shaped0<kAccum, kDev, 4>(p, h, stream, fixed);
+        case 8: return launch_shaped0<kAccum, kDev, 8>(p, h, stream, fixed);
+        case 2 | kShapeRoom: return launch_shaped0<kAccum, kDev, 2 | kShapeRoom>(p, h, stream, fixed);
+        case 4 | kShapeRoom: return launch_shaped0<kAccum, kDev, 4 | kShapeRoom>(p, h, stream, fixed);
+        case 8 | kShapeRoom: return launch_shaped0<kAccum, kDev, 8 | kShapeRoom>(p, h, stream, fixed);
         default: return launch_kernel<0, kAccum, kDev, 0>(p, h, stream);
     }
 }
@@ -2525,7 +2553,10 @@ int scene_shape(const SceneLayout &L, const LaunchHost &h, int max_depth) {
         if (L.off_dmask < 0 || (L.dmask_bytes != 2 && L.dmask_bytes != 4 && L.dmask_bytes != 8) ||
             L.dmask_n != kShapeMaskTexels)
             return 0;
-        return L.dmask_bytes | box;
+        // kShapeFixed: the blob is its class's fixed layout, and the class is
+        // the kernel's (one box with the room shape, several without)
+        const bool fixed = h.fixed_layout && layout_is_fixed(L) && (box != 0) == (L.n_boxes == 1);
+        return L.dmask_bytes | box | (fixed ? kShapeFixed : 0);
     }
     if (max_depth >= 2) {  // the wide masks' lists and the origin-sphere lists take the rays
         if (L.off_gmask < 0 || L.off_glist < 0 || L.off_olist < 0) return 0;
@@ -2656,7 +2687,8 @@ hipError_t allow_large_lds(size_t bytes) {
                      reinterpret_cast<const void *>(&render_kernel<0, false, true, k>),  \
                      reinterpret_cast<const void *>(&render_kernel<0, false, false, k, kLaunchPlain>), \
                      reinterpret_cast<const void *>(&render_kernel<0, false, true, k, kLaunchPlain>), \
-                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k, kLaunchPlain | kLaunchPersistent>)
+                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k, kLaunchPlain | kLaunchPersistent>), \
+                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k | kShapeFixed, kLaunchPlain | kLaunchPersistent>)
 #define RT_WIDE(d) reinterpret_cast<const void *>(&render_kernel<d, false, false, kShapeWide>), \
                    reinterpret_cast<const void *>(&render_kernel<d, false, false, kShapeWide | kShapeRoom>)
     const void *fns[] = {RT_KFN(0), RT_KFN(1), RT_KFN(2), RT_KFN(3), RT_KFN(4),

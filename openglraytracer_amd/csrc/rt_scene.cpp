@@ -1230,17 +1230,40 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     const size_t mask_bits = sph.size() + (box_bits ? boxes.size() : 0);
     lay.dmask_box = 0;
     lay.dmask_bytes = 4;  // (without masks)
+    bool fixed = false;   // the scene takes its layout class's offsets (below)
     if (!sph.empty() && mask_bits <= static_cast<size_t>(kMaskMaxSpheres) && n_live > 0) {
         lay.dmask_bytes = mask_bits <= 16 ? 2 : (mask_bits <= 32 ? 4 : 8);
 #ifndef RT_DMASK_MAXN
 #define RT_DMASK_MAXN 12
 #endif
-        for (int n : {32, 24, 16, 12, 8}) {
-            if (n > RT_DMASK_MAXN) continue;
-            const size_t bytes = static_cast<size_t>(n_live) * 6 * n * n * lay.dmask_bytes;
-            if ((static_cast<size_t>(off) + units(bytes)) * 16 + per_frame <= kMaskLdsBudget) {
-                lay.dmask_n = n;
-                break;
+        // the finest texels whose masks fit beside `head` units of tables
+        const auto texels = [&](int32_t head) {
+            for (int n : {32, 24, 16, 12, 8}) {
+                if (n > RT_DMASK_MAXN) continue;
+                const size_t bytes = static_cast<size_t>(n_live) * 6 * n * n * lay.dmask_bytes;
+                if ((static_cast<size_t>(head) + units(bytes)) * 16 + per_frame <= kMaskLdsBudget) return n;
+            }
+            return 0;
+        };
+        lay.dmask_n = texels(off);
+        // The scene's layout class (rt_internal.h fixed_layout): inside the
+        // maxima, and the padding leaves the masks their texels. Then the
+        // tables move to the class's offsets, the masks follow them, and the
+        // planes, the BVH and its links go behind the masks; else the compact
+        // layout above stands.
+        if (lay.dmask_n > 0 && fixed_counts(static_cast<int>(sph.size()), static_cast<int>(boxes.size()), n_mats, n_lights)) {
+            const FixedLayout f = fixed_layout(boxes.size() == 1);
+            const int32_t n_sph = static_cast<int32_t>(sph.size());
+            const int32_t tail = off - lay.off_lightmat - units(lm.size() * sizeof(LightMatRec));  // planes, BVH, links
+            if (texels(f.off_dmask(n_sph) + tail) == lay.dmask_n) {
+                fixed = true;
+                lay.off_boxes = f.off_boxes;
+                lay.off_mats = f.off_mats;
+                lay.off_lights = f.off_lights;
+                lay.off_lightmat = f.off_lightmat;
+                lay.off_spheres = f.off_spheres;
+                lay.off_smeta = f.off_smeta(n_sph);
+                off = f.off_dmask(n_sph);
             }
         }
     }
@@ -1264,6 +1287,14 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
             std::memcpy(dmask_bytes.data() + i * lay.dmask_bytes, &dmask[i], lay.dmask_bytes);
         off += units(dmask_bytes.size());
         cones.clear();
+    }
+    if (fixed) {  // (the planes stay right before the BVH, as in the compact layout)
+        if (lay.off_bplane >= 0) {
+            lay.off_bplane = off;
+            off += units(bplane.size() * sizeof(float4));
+        }
+        lay.off_bvh = off;     off += units(bvh.size() * sizeof(BvhNode));
+        lay.off_blink = off;   off += units(blink.size() * sizeof(uint32_t));
     }
     const size_t with_cones = (static_cast<size_t>(off) + units(cones.size() * sizeof(ShadowCone))) * 16 + per_frame;
     if (lay.dmask_n == 0 && with_cones <= kConeLdsBudget) {

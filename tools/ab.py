@@ -139,7 +139,7 @@ for cfg in cfgs:
             times[b].append(e0.elapsed_time(e1) / reps)
     for b in builds:
         t = np.array(times[b]) / max(batch, 1, mc_spp)  # per frame (per sample)
-        print("%-8s %-10s median %.4f ms  min %.4f ms  frame %s" % (cfg, b, np.median(t), t.min(), digests[b]),
+        print("%-8s %-10s median %.5f ms  min %.5f ms  frame %s" % (cfg, b, np.median(t), t.min(), digests[b]),
               flush=True)
     for b, (L, ctx) in libs.items():
         L.rt_scene_destroy(state[b])

@@ -61,7 +61,10 @@ int main() {
         const long lds = 16L * (ds.layout.blob_units + 2L * n + 1);
         std::printf("room + %3d spheres: scene build %.3f ms (median of 7), blob %016llx, LDS %ld B (masks %d B)\n", n,
                     ms[3], static_cast<unsigned long long>(hash), lds,
-                    ds.layout.off_dmask >= 0 ? 16 * (ds.layout.blob_units - ds.layout.off_dmask) : 0);
+                    // (the masks end the compact layout; in a class's fixed layout the planes or the BVH follow them)
+                    ds.layout.off_dmask < 0 ? 0 : 16 * ((ds.layout.off_bvh < ds.layout.off_dmask ? ds.layout.blob_units :
+                                                         ds.layout.off_bplane >= 0 ? ds.layout.off_bplane : ds.layout.off_bvh) -
+                                                        ds.layout.off_dmask));
         if (ds.olist_eligible) {  // the origin-sphere lists, built on a scene's first deep render
             std::vector<double> ol;
             std::vector<uint8_t> olist;

@@ -127,8 +127,9 @@ def gate(base, variant, kernels=None):
 # DESIGN.md §3's occupancy table: (row label, kernel) in the order it lists them
 TABLE = [
     ("depth 0, config 2 (room, 2-B masks, > 8 views: device views, plain launch)", "render_kernel<0,false,true,18,1>"),
-    ("depth 0, config 2, 49 or more 1080p views per launch (plain launch, persistent grid)",
-     "render_kernel<0,false,true,18,3>"),
+    ("depth 0, config 2, 49 or more 1080p views per launch (plain launch, persistent grid, the layout class's offsets)",
+     "render_kernel<0,false,true,82,3>"),
+    ("the same with RT_OPT_FIXED_LAYOUT 0, or a scene in the compact layout", "render_kernel<0,false,true,18,3>"),
     ("depth 0, config 2, any other launch shape", "render_kernel<0,false,true,18>"),
     ("depth 0, the shipped scene (2-B masks, 4 boxes, device views, plain launch)", "render_kernel<0,false,true,2,1>"),
     ("depth 0, Monte-Carlo, config 5", "render_kernel<0,true,false,18>"),
