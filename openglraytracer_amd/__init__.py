@@ -88,6 +88,7 @@ def lib():
             "rt_anim_create2": ([vp, vp, vp, vp, i, vp, i, vp, i, i, vp], i),
             "rt_debug_anim_validate": ([vp, vp, vp, i, vp, i, vp, i, i, i], i),
             "rt_debug_anim_host_blob": ([vp, vp, vp, i, vp, i, vp, i, f, vp, C.c_longlong, vp], C.c_longlong),
+            "rt_debug_select_kernel": ([vp, i, vp], i), "rt_debug_last_kernel": ([vp, vp], i),
         }
         for name, (args, res) in sig.items():
             fn = getattr(L, name)
@@ -187,6 +188,22 @@ def anim_host_blob(base, anim, radius=None, materials=None, lights=None, time=0.
     if n < 0:
         raise RTError(int(n), lib().rt_last_error().decode())
     return buf, list(meta)
+
+
+def select_kernel(fields):
+    """rt_debug_select_kernel (host only): (the hook's return value, the key
+    (depth, accum, dev, shape, launch) of the kernel a launch with these 26
+    fields takes)."""
+    f, key = (C.c_int32 * len(fields))(*fields), (C.c_int32 * 5)()
+    return lib().rt_debug_select_kernel(f, len(fields), key), tuple(key)
+
+
+def last_kernel(ctx):
+    """rt_debug_last_kernel: (depth, accum, dev, shape, launch, queued) of the
+    kernel the context's last launch ran."""
+    out = (C.c_int32 * 6)()
+    _check(lib().rt_debug_last_kernel(ctx.handle, out))
+    return tuple(out)
 
 
 def bench_objects(n_spheres, seed=0):

@@ -535,9 +535,31 @@ void reference_view_gl(float time, float unproj[16], float view[16]);
 // llvmpipe evaluates intersect_box_object (column-major)
 void reference_box_transforms(const float pos[3], const float ang[3], float l2w[16], float w2l[16], float nrm[9]);
 
-// rt_kernel.hip. Clears p.sched when the launch does not use the queued
-// distribution (so the caller knows whether the counter slot is in use).
-hipError_t launch_render(LaunchParams &p, const LaunchHost &h, int max_depth, hipStream_t stream);
+// rt_kernel.hip. The render kernels stand in one table, a row per
+// instantiation of render_kernel<depth, accum, dev, shape, launch> (shape:
+// kShape* bits, launch: kLaunch* bits) with the kernel's address.
+struct KernelKey {  // (five int32_t and no padding: the debug hooks copy it out as such)
+    int32_t depth, accum, dev, shape, launch;
+};
+struct KernelRow {
+    KernelKey key;
+    void (*kernel)(LaunchParams);
+    const void *fn() const { return reinterpret_cast<const void *>(kernel); }  // as the HIP runtime takes it
+};
+const KernelRow *find_kernel(const KernelKey &k);  // null: no such instantiation
+// The kernel a launch takes: `tiled` (or queued), and for a depth-0 batch
+// where `candidate` is set `persistent` instead when persistent_groups, at
+// that kernel's resident work-groups, gives a grid. False: a launch no kernel
+// serves (device-side views above depth 1 or with accumulation).
+struct KernelChoice {
+    KernelKey tiled, persistent;
+    bool candidate;
+};
+bool select_kernel(const LaunchParams &p, const LaunchHost &h, int max_depth, KernelChoice &c);
+// Launches the row select_kernel names (`ran`: its key). Clears p.sched when
+// the launch does not use the queued distribution (so the caller knows
+// whether the counter slot is in use).
+hipError_t launch_render(LaunchParams &p, const LaunchHost &h, int max_depth, hipStream_t stream, KernelKey &ran);
 // LDS of a one-view work-group: the blob's staged part and the view's records.
 size_t lds_bytes(const SceneLayout &L, bool lean = false);
 // Views of one scene a queued launch at this depth holds (deep frames: every
@@ -625,6 +647,7 @@ struct rt_context {
     bool sched_used[rtamd::kSchedSlots] = {};
     bool last_queued = false;   // the last launch used its slot (rt_debug_last_queued)
     int last_shape = 0;         // the last launch's scene shape (rt_debug_last_scene_shape)
+    rtamd::KernelKey last_kernel{};  // the row the last launch ran (rt_debug_last_kernel)
     std::vector<struct rt_scene *> scenes;  // live scenes (detached by rt_destroy)
 };
 

@@ -36,8 +36,8 @@
 #include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <cstring>
 #include <string>
-#include <type_traits>
 
 #include "rt_internal.h"
 
@@ -2433,115 +2433,65 @@ int queued_views_for(const void *fn, const SceneLayout &L, bool lean) {
     return n;
 }
 
-template <int kDepth, bool kAccum, bool kDev = false, int kShape = 0, int kLaunch = 0>
-hipError_t launch_kernel(LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
-    constexpr bool kLean = kLeanViews(kShape);
-    size_t lds = lds_bytes(p.layout, kLean);
-    const void *fn = reinterpret_cast<const void *>(&render_kernel<kDepth, kAccum, kDev, kShape, kLaunch>);
+// The render kernels: one row per instantiation, and the only list of them
+// (taking a kernel's address here is what instantiates it). select_kernel
+// names a launch's row, find_kernel looks it up, launch_kernel runs it.
+#define RT_ROW(d, accum, dev, shape, launch) \
+    {{d, accum, dev, shape, launch}, &render_kernel<d, accum, dev, shape, launch>}
+#define RT_KFN(d) RT_ROW(d, false, false, 0, 0), RT_ROW(d, true, false, 0, 0)  // general: a frame, Monte-Carlo
+// a depth-0 scene shape: tiled (views in the arguments, Monte-Carlo, device
+// views), plain (either view source), persistent (without and with kShapeFixed)
+#define RT_SHAPES(k)                                                                           \
+    RT_ROW(0, false, false, k, 0), RT_ROW(0, true, false, k, 0), RT_ROW(0, false, true, k, 0), \
+        RT_ROW(0, false, false, k, kLaunchPlain), RT_ROW(0, false, true, k, kLaunchPlain),     \
+        RT_ROW(0, false, true, k, kLaunchPlain | kLaunchPersistent),                           \
+        RT_ROW(0, false, true, k | kShapeFixed, kLaunchPlain | kLaunchPersistent)
+#define RT_WIDE(d) RT_ROW(d, false, false, kShapeWide, 0), RT_ROW(d, false, false, kShapeWide | kShapeRoom, 0)
+constexpr KernelRow kKernels[] = {
+    RT_KFN(0), RT_KFN(1), RT_KFN(2), RT_KFN(3), RT_KFN(4), RT_KFN(5), RT_KFN(6), RT_KFN(7), RT_KFN(8), RT_KFN(9),
+    RT_ROW(0, false, true, 0, 0), RT_ROW(1, false, true, 0, 0),  // device views, general
+    RT_SHAPES(2), RT_SHAPES(4), RT_SHAPES(8),
+    RT_SHAPES(2 | kShapeRoom), RT_SHAPES(4 | kShapeRoom), RT_SHAPES(8 | kShapeRoom),
+    RT_WIDE(2), RT_WIDE(3), RT_WIDE(4), RT_WIDE(5), RT_WIDE(6), RT_WIDE(7), RT_WIDE(8), RT_WIDE(9)};
+#undef RT_ROW
+#undef RT_KFN
+#undef RT_SHAPES
+#undef RT_WIDE
+
+hipError_t launch_row(const KernelRow &row, dim3 grid, size_t lds, LaunchParams &p, hipStream_t stream) {
+    void *args[] = {&p};
+    const hipError_t e = hipLaunchKernel(row.fn(), grid, dim3(kThreads), args, lds, stream);
+    (void)hipGetLastError();  // (e is the launch's own status; no sticky error for a later check)
+    return e;
+}
+
+// The tiled launch of a row, or its queued one (the recursive depths).
+hipError_t launch_kernel(const KernelRow &row, LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
+    const bool lean = kLeanViews(row.key.shape);
+    size_t lds = lds_bytes(p.layout, lean);
     dim3 grid((p.width + kTileX - 1) / kTileX, (p.slice_rows + kTileY - 1) / kTileY, p.n_views);
     const int wave_tiles = ((p.width + 7) / 8) * ((p.slice_rows + 7) / 8) * p.n_views;
-    const int resident = h.n_cu > 0 ? groups_per_cu(fn, lds) * h.n_cu : 0;
+    const int resident = h.n_cu > 0 ? groups_per_cu(row.fn(), lds) * h.n_cu : 0;
     // queued: more wave tiles than resident waves, every queue has a wave (a
     // queue without one would leave its tiles unrendered), and for several
     // views: one scene (staged once) and every view's constants in LDS at the
     // same resident work-groups (queued_views)
     bool one_scene = p.n_views <= kMaxViews;
     for (int k = 0; k < p.n_views && one_scene; ++k) one_scene = p.view[k].blob == nullptr;
-    if (kQueuedDepth(kDepth) && p.sched && wave_tiles > resident * (kThreads / 64) &&
+    if (kQueuedDepth(row.key.depth) && p.sched && wave_tiles > resident * (kThreads / 64) &&
         resident * (kThreads / 64) >= kQueues &&
-        (p.n_views == 1 || (one_scene && queued_views_for(fn, p.layout, kLean) >= p.n_views))) {
+        (p.n_views == 1 || (one_scene && queued_views_for(row.fn(), p.layout, lean) >= p.n_views))) {
         grid = dim3(resident, 1, 1);
-        lds = queued_lds_bytes(p.layout, kLean, p.n_views);
+        lds = queued_lds_bytes(p.layout, lean, p.n_views);
     } else {
         p.sched = nullptr;
     }
-    hipLaunchKernelGGL((render_kernel<kDepth, kAccum, kDev, kShape, kLaunch>), grid, dim3(kThreads), lds, stream, p);
-    return hipGetLastError();
+    return launch_row(row, grid, lds, p, stream);
 }
 
 // LDS of a persistent launch: the scene and one view's records per wave.
 size_t persistent_lds_bytes(const LaunchParams &p) {
     return (static_cast<size_t>(p.layout.blob_units) + static_cast<size_t>(kThreads / 64) * p.n_frame_consts) * sizeof(float4);
-}
-
-// The depth-0 kernels in the scene's shape (scene_shape): 2-, 4- or 8-byte
-// LDS masks, one box or several; anything else runs the general kernel.
-// A shaped kernel also takes the launch's shape (launch_shape) where one
-// applies: the plain launch, never with accumulation.
-// A plain device-view batch takes the persistent distribution where
-// persistent_groups says so: the grid is the kernel's resident work-groups
-// (or RT_OPT_PERSISTENT0's cap), the LDS the scene and a view's records per
-// wave.
-// `fixed`: the scene's shape carried kShapeFixed; the persistent kernels are
-// instantiated with it, the tiled ones read LaunchParams::layout (which
-// describes the same blob).
-template <bool kAccum, bool kDev, int kShape>
-hipError_t launch_shaped0(LaunchParams &p, const LaunchHost &h, hipStream_t stream, bool fixed) {
-    if constexpr (!kAccum) {
-        if ((launch_shape(p, h, 0) & kLaunchPlain) != 0) {
-            if constexpr (kDev) {
-                constexpr int kPersistent = kLaunchPlain | kLaunchPersistent;
-                const size_t lds = persistent_lds_bytes(p);
-                if (h.persistent0 > 0 && p.sched && lds <= kMaxLds && h.n_cu > 0) {  // (else: no occupancy query)
-                    const auto run = [&](auto shape) {  // the work-groups launched, 0: none
-                        constexpr int kS = decltype(shape)::value;
-                        const void *fn = reinterpret_cast<const void *>(&render_kernel<0, false, true, kS, kPersistent>);
-                        const int groups = persistent_groups(p, h, groups_per_cu(fn, lds) * h.n_cu);
-                        if (groups > 0)
-                            hipLaunchKernelGGL((render_kernel<0, false, true, kS, kPersistent>), dim3(groups),
-                                               dim3(kThreads), lds, stream, p);
-                        return groups;
-                    };
-                    const int groups = fixed ? run(std::integral_constant<int, kShape | kShapeFixed>{})
-                                             : run(std::integral_constant<int, kShape>{});
-                    if (groups > 0) return hipGetLastError();
-                }
-            }
-            return launch_kernel<0, false, kDev, kShape, kLaunchPlain>(p, h, stream);
-        }
-    }
-    return launch_kernel<0, kAccum, kDev, kShape>(p, h, stream);
-}
-template <bool kAccum, bool kDev>
-hipError_t launch_depth0(LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
-    const int shape = scene_shape(p.layout, h, 0);
-    const bool fixed = (shape & kShapeFixed) != 0;
-    switch (shape & ~kShapeFixed) {
-        case 2: return launch_shaped0<kAccum, kDev, 2>(p, h, stream, fixed);
-        case 4: return launch_shaped0<kAccum, kDev, 4>(p, h, stream, fixed);
-        case 8: return launch_shaped0<kAccum, kDev, 8>(p, h, stream, fixed);
-        case 2 | kShapeRoom: return launch_shaped0<kAccum, kDev, 2 | kShapeRoom>(p, h, stream, fixed);
-        case 4 | kShapeRoom: return launch_shaped0<kAccum, kDev, 4 | kShapeRoom>(p, h, stream, fixed);
-        case 8 | kShapeRoom: return launch_shaped0<kAccum, kDev, 8 | kShapeRoom>(p, h, stream, fixed);
-        default: return launch_kernel<0, kAccum, kDev, 0>(p, h, stream);
-    }
-}
-
-// The recursive kernels in the wide-mask shape (scene_shape), else general.
-template <int kDepth>
-hipError_t launch_deep(LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
-    switch (scene_shape(p.layout, h, kDepth)) {
-        case kShapeWide: return launch_kernel<kDepth, false, false, kShapeWide>(p, h, stream);
-        case kShapeWide | kShapeRoom: return launch_kernel<kDepth, false, false, kShapeWide | kShapeRoom>(p, h, stream);
-        default: return launch_kernel<kDepth, false, false, 0>(p, h, stream);
-    }
-}
-
-template <int kDepth>
-hipError_t launch_depth(LaunchParams &p, const LaunchHost &h, hipStream_t stream) {
-    if (p.views_dev) {  // a device-side view batch (render_batch_impl: depth 0-1, no accumulation)
-        if constexpr (kDepth == 0) {
-            if (p.spp == 0) return launch_depth0<false, true>(p, h, stream);
-        } else if constexpr (kDepth == 1) {
-            if (p.spp == 0) return launch_kernel<kDepth, false, true>(p, h, stream);
-        }
-        return hipErrorInvalidValue;
-    }
-    if constexpr (kDepth == 0) return p.spp > 0 ? launch_depth0<true, false>(p, h, stream) : launch_depth0<false, false>(p, h, stream);
-    if constexpr (kDepth >= 2) {
-        if (p.spp == 0) return launch_deep<kDepth>(p, h, stream);
-    }
-    return p.spp > 0 ? launch_kernel<kDepth, true>(p, h, stream) : launch_kernel<kDepth, false>(p, h, stream);
 }
 
 }  // namespace
@@ -2602,41 +2552,63 @@ size_t lds_bytes(const SceneLayout &L, bool lean) {
     return (static_cast<size_t>(L.blob_units) + view_units(L, lean)) * sizeof(float4);
 }
 
-int queued_views(const SceneLayout &L, int max_depth) {
-    const void *fn = nullptr;
-    switch (max_depth) {  // (the view-batch kernels: no accumulation)
-        case 2: fn = reinterpret_cast<const void *>(&render_kernel<2, false>); break;
-        case 3: fn = reinterpret_cast<const void *>(&render_kernel<3, false>); break;
-        case 4: fn = reinterpret_cast<const void *>(&render_kernel<4, false>); break;
-        case 5: fn = reinterpret_cast<const void *>(&render_kernel<5, false>); break;
-        case 6: fn = reinterpret_cast<const void *>(&render_kernel<6, false>); break;
-        case 7: fn = reinterpret_cast<const void *>(&render_kernel<7, false>); break;
-        case 8: fn = reinterpret_cast<const void *>(&render_kernel<8, false>); break;
-        case 9: fn = reinterpret_cast<const void *>(&render_kernel<9, false>); break;
-        default: return 1;
-    }
-    static_assert(!kQueuedDepth(1) && kQueuedDepth(2), "queued from depth 2");
-    return queued_views_for(fn, L, false);  // (the general kernels: full view records)
+const KernelRow *find_kernel(const KernelKey &k) {
+    for (const KernelRow &row : kKernels)
+        if (std::memcmp(&row.key, &k, sizeof k) == 0) return &row;  // (five int32_t: no padding)
+    return nullptr;
 }
 
-hipError_t launch_render(LaunchParams &p, const LaunchHost &h, int max_depth, hipStream_t stream) {
+int queued_views(const SceneLayout &L, int max_depth) {
+    // (the view-batch kernels: no accumulation; the general ones: full view records)
+    const KernelRow *row = kQueuedDepth(max_depth) ? find_kernel({max_depth, 0, 0, 0, 0}) : nullptr;
+    return row ? queued_views_for(row->fn(), L, false) : 1;
+}
+
+// Which kernel a launch takes (no HIP call: rt_debug_select_kernel runs it
+// without a device). Depth 0, the kernels in the scene's shape (scene_shape):
+// 2-, 4- or 8-byte LDS masks, one box or several; anything else runs the
+// general kernel. A shaped kernel also takes the launch's shape
+// (launch_shape) where one applies: the plain launch, never with
+// accumulation. A plain device-view batch takes the persistent distribution
+// where persistent_groups says so: the grid is the kernel's resident
+// work-groups (or RT_OPT_PERSISTENT0's cap), the LDS the scene and a view's
+// records per wave. Only the persistent kernels are instantiated with
+// kShapeFixed; the tiled ones read LaunchParams::layout (which describes the
+// same blob). Depth 1: general. Depths 2-9: the wide-mask shape
+// (scene_shape) or general, Monte-Carlo always general.
+bool select_kernel(const LaunchParams &p, const LaunchHost &h, int max_depth, KernelChoice &c) {
+    const int accum = p.spp > 0, dev = p.views_dev != nullptr;
+    // a device-side view batch (render_batch_impl): depth 0-1, no accumulation
+    if (dev && (max_depth > 1 || accum)) return false;
+    const int shape = max_depth == 1 || (max_depth >= 2 && accum) ? 0 : scene_shape(p.layout, h, max_depth);
+    c = KernelChoice{{max_depth, accum, dev, shape & ~kShapeFixed, 0}, {}, false};
+    if (max_depth != 0 || shape == 0 || accum || (launch_shape(p, h, 0) & kLaunchPlain) == 0) return true;
+    c.tiled.launch = kLaunchPlain;
+    // (h.n_cu: without it no occupancy query, so no resident grid)
+    c.candidate = dev && h.persistent0 > 0 && p.sched && persistent_lds_bytes(p) <= kMaxLds && h.n_cu > 0;
+    if (c.candidate) c.persistent = {0, 0, 1, shape, kLaunchPlain | kLaunchPersistent};
+    return true;
+}
+
+hipError_t launch_render(LaunchParams &p, const LaunchHost &h, int max_depth, hipStream_t stream, KernelKey &ran) {
     if (p.slice_rows <= 0) {  // the whole launch as one slice
         p.slice_begin = 0;
         p.slice_rows = p.n_rows;
     }
-    switch (max_depth) {
-        case 0: return launch_depth<0>(p, h, stream);
-        case 1: return launch_depth<1>(p, h, stream);
-        case 2: return launch_depth<2>(p, h, stream);
-        case 3: return launch_depth<3>(p, h, stream);
-        case 4: return launch_depth<4>(p, h, stream);
-        case 5: return launch_depth<5>(p, h, stream);
-        case 6: return launch_depth<6>(p, h, stream);
-        case 7: return launch_depth<7>(p, h, stream);
-        case 8: return launch_depth<8>(p, h, stream);
-        case 9: return launch_depth<9>(p, h, stream);
-        default: return hipErrorInvalidValue;
+    KernelChoice c;
+    if (!select_kernel(p, h, max_depth, c)) return hipErrorInvalidValue;
+    // (a key the table lacks is an error, never another kernel)
+    const KernelRow *row = find_kernel(c.candidate ? c.persistent : c.tiled);
+    if (row && c.candidate) {
+        const size_t lds = persistent_lds_bytes(p);
+        const int groups = persistent_groups(p, h, groups_per_cu(row->fn(), lds) * h.n_cu);
+        ran = row->key;
+        if (groups > 0) return launch_row(*row, dim3(groups), lds, p, stream);
+        row = find_kernel(c.tiled);
     }
+    if (!row) return hipErrorInvalidValue;
+    ran = row->key;
+    return launch_kernel(*row, p, h, stream);
 }
 
 // Kernel-argument self-test (rt_create): the launch parameter block is larger
@@ -2680,29 +2652,8 @@ int check_kernarg_block(hipStream_t stream) {
 // (gfx950 has 160 KiB per CU). Best effort: a failure only lowers the largest
 // scene that fits, which rt_scene_create checks.
 hipError_t allow_large_lds(size_t bytes) {
-#define RT_KFN(d) reinterpret_cast<const void *>(&render_kernel<d, false>), \
-                  reinterpret_cast<const void *>(&render_kernel<d, true>)
-#define RT_SHAPES(k) reinterpret_cast<const void *>(&render_kernel<0, false, false, k>), \
-                     reinterpret_cast<const void *>(&render_kernel<0, true, false, k>),  \
-                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k>),  \
-                     reinterpret_cast<const void *>(&render_kernel<0, false, false, k, kLaunchPlain>), \
-                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k, kLaunchPlain>), \
-                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k, kLaunchPlain | kLaunchPersistent>), \
-                     reinterpret_cast<const void *>(&render_kernel<0, false, true, k | kShapeFixed, kLaunchPlain | kLaunchPersistent>)
-#define RT_WIDE(d) reinterpret_cast<const void *>(&render_kernel<d, false, false, kShapeWide>), \
-                   reinterpret_cast<const void *>(&render_kernel<d, false, false, kShapeWide | kShapeRoom>)
-    const void *fns[] = {RT_KFN(0), RT_KFN(1), RT_KFN(2), RT_KFN(3), RT_KFN(4),
-                         RT_KFN(5), RT_KFN(6), RT_KFN(7), RT_KFN(8), RT_KFN(9),
-                         reinterpret_cast<const void *>(&render_kernel<0, false, true>),
-                         reinterpret_cast<const void *>(&render_kernel<1, false, true>),
-                         RT_SHAPES(2), RT_SHAPES(4), RT_SHAPES(8),
-                         RT_SHAPES(2 | kShapeRoom), RT_SHAPES(4 | kShapeRoom), RT_SHAPES(8 | kShapeRoom),
-                         RT_WIDE(2), RT_WIDE(3), RT_WIDE(4), RT_WIDE(5), RT_WIDE(6), RT_WIDE(7), RT_WIDE(8), RT_WIDE(9)};
-#undef RT_KFN
-#undef RT_SHAPES
-#undef RT_WIDE
-    for (const void *f : fns)
-        (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    for (const KernelRow &row : kKernels)
+        (void)hipFuncSetAttribute(row.fn(), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
     (void)hipGetLastError();  // do not leak a sticky error into the next launch check
     return hipSuccess;
 }
@@ -2742,8 +2693,8 @@ extern "C" int rt_debug_phase_read(void *dst, size_t bytes) {
 }
 extern "C" int rt_debug_occupancy(size_t lds) {
     int n = -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(&rtamd::render_kernel<0, false>),
-                                                     rtamd::kThreads, lds) != hipSuccess)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, rtamd::find_kernel({0, 0, 0, 0, 0})->fn(), rtamd::kThreads, lds) !=
+        hipSuccess)
         return -1;
     return n;
 }

@@ -3,6 +3,8 @@
     python tools/resources.py [LIB.so | BUILD ...]        (default: the in-tree library)
     python tools/resources.py --gate BASE.so VARIANT.so   exit 1 if VARIANT spills more
     python tools/resources.py --markdown [BUILD]          DESIGN.md §3's occupancy table
+    python tools/resources.py --text BASE VARIANT         exit 1 unless both (.so or .o) hold the same device
+                                                          functions with the same instructions
 
 Reads the gfx950 code objects out of the library's .hip_fatbin section
 (llvm-objcopy + clang-offload-bundler) and its kernel metadata notes
@@ -36,7 +38,7 @@ TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 def lib_path(spec):
     if spec in ("main", None):
         return os.path.join(ROOT, "openglraytracer_amd", "libopenglraytracer_amd.so")
-    if spec.endswith(".so"):
+    if spec.endswith((".so", ".o")):
         return spec
     return os.path.join(ROOT, "_ab", spec, "libopenglraytracer_amd.so")
 
@@ -62,25 +64,30 @@ def kernel_name(mangled):
     return mangled
 
 
+def code_objects(so, d):
+    """The gfx950 code objects of a library or object file, unbundled into directory d."""
+    fb = os.path.join(d, "fb.bin")
+    subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fb, so, os.path.join(d, "x")],
+                   check=True, capture_output=True)
+    # one bundle per translation unit with kernels, back to back in the section
+    with open(fb, "rb") as f:
+        data = f.read()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    starts = [m.start() for m in re.finditer(re.escape(magic), data)]
+    for i, at in enumerate(starts):
+        part, co = os.path.join(d, "fb%d.bin" % i), os.path.join(d, "k%d.co" % i)
+        with open(part, "wb") as f:
+            f.write(data[at:starts[i + 1] if i + 1 < len(starts) else len(data)])
+        subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + part,
+                        "--targets=" + TARGET, "--output=" + co], check=True, capture_output=True)
+        yield co
+
+
 def resources(so):
     """{kernel: {"vgpr", "sgpr", "scratch", "waves_per_simd"}} of the library's gfx950 code object."""
     with tempfile.TemporaryDirectory() as d:
-        fb, co = os.path.join(d, "fb.bin"), os.path.join(d, "k.co")
-        subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fb, so, os.path.join(d, "x")],
-                       check=True, capture_output=True)
-        # one bundle per translation unit with kernels, back to back in the section
-        with open(fb, "rb") as f:
-            data = f.read()
-        magic, notes = b"__CLANG_OFFLOAD_BUNDLE__", ""
-        starts = [m.start() for m in re.finditer(re.escape(magic), data)]
-        for i, at in enumerate(starts):
-            part = os.path.join(d, "fb%d.bin" % i)
-            with open(part, "wb") as f:
-                f.write(data[at:starts[i + 1] if i + 1 < len(starts) else len(data)])
-            subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + part,
-                            "--targets=" + TARGET, "--output=" + co], check=True, capture_output=True)
-            notes += subprocess.run([LLVM + "/llvm-readelf", "--notes", co], check=True, capture_output=True,
-                                    text=True).stdout
+        notes = "".join(subprocess.run([LLVM + "/llvm-readelf", "--notes", co], check=True, capture_output=True,
+                                       text=True).stdout for co in code_objects(so, d))
     out, cur = {}, {}
     for line in notes.splitlines():
         m = re.match(r"\s*-?\s*\.(name|vgpr_count|sgpr_count|private_segment_fixed_size):\s+(\S+)", line)
@@ -95,6 +102,35 @@ def resources(so):
         if "vgpr" in r:
             r["waves_per_simd"] = min(8, 512 // max(8, -(-r["vgpr"] // 8) * 8))
     return {k: v for k, v in out.items() if k.startswith(("render_kernel", "animate_kernel"))}
+
+
+def texts(so):
+    """{symbol: its instructions} of the file's gfx950 code objects (llvm-objdump -d, without the
+    addresses and encodings)."""
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        for co in code_objects(so, d):
+            cur = None
+            dis = subprocess.run([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", co],
+                                 check=True, capture_output=True, text=True).stdout
+            for line in dis.splitlines():
+                m = re.match(r"^(?:[0-9a-f]+ )?<([^>]+)>:$", line)
+                if m:
+                    cur = out.setdefault(m.group(1), [])
+                elif cur is not None and line.strip():
+                    cur.append(re.sub(r"\s*//.*$", "", line).strip())  # (the address and encoding comment)
+    return out
+
+
+def same_text(base, variant):
+    """Prints how the two files' device functions compare; True when both have the same symbols with
+    the same instruction text (their order in the code object may differ)."""
+    a, b = texts(lib_path(base)), texts(lib_path(variant))
+    odd = sorted(set(a) ^ set(b)) + sorted(k for k in set(a) & set(b) if a[k] != b[k])
+    print("device functions: %d and %d; on one side only or with other instructions: %d" % (len(a), len(b), len(odd)))
+    for k in odd:
+        print("  " + k)
+    return not odd
 
 
 def fmt(name, r):
@@ -163,6 +199,8 @@ def main():
     if args[:1] == ["--markdown"]:
         print(markdown(args[1] if len(args) > 1 else "main"))
         return
+    if args[:1] == ["--text"]:
+        sys.exit(0 if same_text(args[1], args[2]) else 1)
     if args[:1] == ["--gate"]:
         bad = gate(args[1], args[2])
         for k, x, y in bad:
