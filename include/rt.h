@@ -384,6 +384,59 @@ int rt_render_accumulate(rt_context *ctx, const rt_scene *scene, const rt_view *
                          int max_depth, int spp, int sample_offset, uint32_t seed, int jitter, int row_begin,
                          int row_end, float *accum_device, void *hip_stream);
 
+/* ---- primary-hit buffers and pixel picking ------------------------------
+ * What the kernel finds on the way to a pixel's colour, instead of the
+ * colour: per pixel, the object its camera ray hits first
+ * (get_closest_collision, raytrace_compute.glsl:738-782), the collision's
+ * normal and world position, and which lights are occluded from there
+ * (the shadow ray of :807-819). For picking, for depth and normal guides of a
+ * denoiser over rt_render_accumulate's means, and for debugging a colour.
+ *
+ * Layout: rt_render's — row-major, row 0 = GL's bottom row, rows
+ * [row_begin, row_end), pixel (x, y) at (y - row_begin) * width + x. Three
+ * planes, each optional (NULL; not all three): `hits`, one rt_hit per pixel;
+ * `normals` and `points`, 4 floats per pixel (x, y, z, 0), (0, 0, 0, 0) for a
+ * miss. Every pixel of the row range is written, misses included.
+ * The shadow bits cover every light: also one without diffuse and specular
+ * colour, whose shadow ray a colour render never casts because it cannot
+ * change the colour. With flags = 0 no shadow ray is cast and shadow is 0.
+ * RT_OPT_OUTPUT does not apply (the records' formats are fixed);
+ * RT_OPT_CULLING applies and leaves the output identical; no other context
+ * option changes it. out_is_device, hip_stream and the errors are
+ * rt_render_view's (RT_ERR_INVALID for a NULL pointer, a bad size or row
+ * range, all three planes NULL, or an unknown flag bit); host planes go
+ * through a grow-only device buffer of the context, so no allocation happens
+ * after the first call at a given size. With RT_OPT_TIMING,
+ * rt_last_kernel_ms covers the hits launch. The hits kernel is not a row of
+ * the render kernels' table: rt_debug_last_kernel (and the other
+ * rt_debug_last_* hooks) keep reporting the last render launch. */
+typedef struct rt_hit {      /* 16 bytes per pixel */
+    int32_t  object;         /* index into the scene's objs[], -1 = the ray hit nothing          */
+    float    t;              /* get_closest_collision's t (:738-782); 0 for a miss               */
+    uint32_t shadow;         /* bit j: light j is occluded from the hit point (:807-819), j < 16 */
+    int32_t  material;       /* objs[object].material; -1 for a miss                             */
+} rt_hit;
+#define RT_HITS_SHADOW 1     /* flags: compute rt_hit.shadow (otherwise 0, and no shadow ray is cast) */
+int rt_render_hits_view(rt_context *ctx, const rt_scene *scene, const rt_view *view, int width, int height,
+                        int row_begin, int row_end, int flags, rt_hit *hits, float *normals, float *points,
+                        int out_is_device, void *hip_stream);
+/* cam == NULL: the reference orbit camera at `time`. */
+int rt_render_hits(rt_context *ctx, const rt_scene *scene, const rt_camera *cam, float time, int width, int height,
+                   int row_begin, int row_end, int flags, rt_hit *hits, float *normals, float *points,
+                   int out_is_device, void *hip_stream);
+/* rt_render_hits with the objects at `time` too, as rt_render_animated: the
+ * animate kernel on the next frame slot, then the hits launch on that slot. */
+int rt_render_hits_animated(rt_context *ctx, rt_anim *anim, const rt_camera *cam, float time, int width, int height,
+                            int row_begin, int row_end, int flags, rt_hit *hits, float *normals, float *points,
+                            int out_is_device, void *hip_stream);
+/* The records of one pixel (x, y in the layout's convention: y = 0 is the
+ * bottom row) into host memory, synchronously on the context's stream; hit,
+ * normal and point may each be NULL, not all three. Renders the pixel's row
+ * into the context's buffer and copies 48 bytes back. RT_ERR_INVALID for a
+ * pixel outside the frame. */
+int rt_pick(rt_context *ctx, const rt_scene *scene, const rt_view *view, int width, int height, int x, int y,
+            int flags, rt_hit *hit, float normal[3], float point[3]);
+
 /* ---- one frame on several GPUs of this process ----
  * The reference renders a frame with one glDispatchCompute(W, H, 1) +
  * glFinish (OpenGLRaytracer/main.cpp:228-238). A multi-GPU group deals the

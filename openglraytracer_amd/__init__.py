@@ -89,6 +89,10 @@ def lib():
             "rt_debug_anim_validate": ([vp, vp, vp, i, vp, i, vp, i, i, i], i),
             "rt_debug_anim_host_blob": ([vp, vp, vp, i, vp, i, vp, i, f, vp, C.c_longlong, vp], C.c_longlong),
             "rt_debug_select_kernel": ([vp, i, vp], i), "rt_debug_last_kernel": ([vp, vp], i),
+            "rt_render_hits_view": ([vp, vp, vp, i, i, i, i, i, vp, vp, vp, i, vp], i),
+            "rt_render_hits": ([vp, vp, vp, f, i, i, i, i, i, vp, vp, vp, i, vp], i),
+            "rt_render_hits_animated": ([vp, vp, vp, f, i, i, i, i, i, vp, vp, vp, i, vp], i),
+            "rt_pick": ([vp, vp, vp, i, i, i, i, i, vp, vp, vp], i),
         }
         for name, (args, res) in sig.items():
             fn = getattr(L, name)
@@ -533,6 +537,81 @@ def render_device(ctx, scene, out_ptr, width, height, max_depth=0, view=None, ro
     _check(lib().rt_render_view(ctx.handle, scene.handle, C.byref(view), width, height, max_depth,
                                 r0, r1, C.c_void_p(out_ptr), 1,
                                 C.c_void_p(stream) if stream else None))
+
+
+# ---- primary-hit buffers and picking (rt_render_hits*, rt_pick) -------------
+HIT_PLANES = ("hits", "normals", "points")
+
+
+def _hit_planes(planes, rows, width):
+    """Host arrays for the requested planes, in HIT_PLANES' order (None: not wanted)."""
+    unknown = [p for p in planes if p not in HIT_PLANES]
+    if unknown or not planes:
+        raise ValueError("planes: a non-empty choice of %s, not %r" % (HIT_PLANES, tuple(planes)))
+    shape = (max(rows, 1), max(width, 1))
+    return [None if name not in planes else
+            (np.zeros(shape, abi.HIT_DTYPE) if name == "hits" else np.zeros(shape + (4,), np.float32))
+            for name in HIT_PLANES]
+
+
+def _plane_ptrs(arrays):
+    return [C.c_void_p(a.ctypes.data) if a is not None else None for a in arrays]
+
+
+def render_hits(ctx, scene, width, height, time=0.0, camera=None, view=None, rows=None, shadow=True,
+                planes=HIT_PLANES):
+    """rt_render_hits_view to host arrays, synchronously: for rows [r0, r1) the
+    planes asked for, in the order of `planes` — "hits" (r1-r0, width) of
+    abi.HIT_DTYPE (object, t, shadow, material), "normals" and "points"
+    (r1-r0, width, 4) float32. shadow=False: no shadow rays, shadow = 0."""
+    r0, r1 = rows if rows is not None else (0, height)
+    arrays = _hit_planes(planes, r1 - r0, width)
+    if view is None:
+        view = make_view(camera, time)
+    _check(lib().rt_render_hits_view(ctx.handle, scene.handle, C.byref(view), width, height, r0, r1,
+                                     abi.RT_HITS_SHADOW if shadow else 0, *_plane_ptrs(arrays), 0, None))
+    by_name = dict(zip(HIT_PLANES, arrays))
+    return tuple(by_name[name][: r1 - r0, :width] for name in planes)
+
+
+def render_hits_device(ctx, scene, width, height, hits_ptr=None, normals_ptr=None, points_ptr=None, view=None,
+                       rows=None, shadow=True, stream=None):
+    """rt_render_hits_view into device memory (e.g. torch tensors' data_ptr();
+    16 bytes per pixel and plane, None: the plane is not wanted); with `stream`
+    (a hipStream_t as int) the call is asynchronous on that stream."""
+    r0, r1 = rows if rows is not None else (0, height)
+    if view is None:
+        view = make_view(None, 0.0)
+    ptrs = [C.c_void_p(p) if p else None for p in (hits_ptr, normals_ptr, points_ptr)]
+    _check(lib().rt_render_hits_view(ctx.handle, scene.handle, C.byref(view), width, height, r0, r1,
+                                     abi.RT_HITS_SHADOW if shadow else 0, *ptrs, 1,
+                                     C.c_void_p(stream) if stream else None))
+
+
+def render_hits_animated(ctx, anim, width, height, time=0.0, camera=None, rows=None, shadow=True,
+                         planes=HIT_PLANES):
+    """rt_render_hits_animated to host arrays (render_hits' result): the objects
+    and (with camera None) the orbit camera at `time`."""
+    r0, r1 = rows if rows is not None else (0, height)
+    arrays = _hit_planes(planes, r1 - r0, width)
+    _check(lib().rt_render_hits_animated(ctx.handle, anim.handle, C.byref(camera) if camera is not None else None,
+                                         time, width, height, r0, r1, abi.RT_HITS_SHADOW if shadow else 0,
+                                         *_plane_ptrs(arrays), 0, None))
+    by_name = dict(zip(HIT_PLANES, arrays))
+    return tuple(by_name[name][: r1 - r0, :width] for name in planes)
+
+
+def pick(ctx, scene, width, height, x, y, view=None, time=0.0, shadow=True):
+    """rt_pick: pixel (x, y)'s records (y = 0: the bottom row) as (abi.Hit,
+    normal (3,), point (3,)); view None: the orbit camera at `time`."""
+    if view is None:
+        view = make_view(None, time)
+    hit = abi.Hit()
+    normal, point = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    _check(lib().rt_pick(ctx.handle, scene.handle, C.byref(view), width, height, x, y,
+                         abi.RT_HITS_SHADOW if shadow else 0, C.byref(hit), C.c_void_p(normal.ctypes.data),
+                         C.c_void_p(point.ctypes.data)))
+    return hit, normal, point
 
 
 def render_batch(ctx, scene, out_ptr, width, height, max_depth, views, block_rows=8, n_shards=1,

@@ -78,6 +78,19 @@ class ObjectAnim(C.Structure):
     _fields_ = [("scale", AnimChannel), ("position", AnimChannel * 3), ("angles", AnimChannel * 3)]
 
 
+RT_HITS_SHADOW = 1
+
+
+class Hit(C.Structure):
+    """rt_hit: one pixel's primary hit (rt_render_hits, rt_pick), 16 bytes."""
+    _fields_ = [("object", C.c_int32), ("t", C.c_float), ("shadow", C.c_uint32), ("material", C.c_int32)]
+
+
+# the same record as a numpy dtype (the `hits` plane of render_hits)
+HIT_DTYPE = np.dtype([("object", np.int32), ("t", np.float32), ("shadow", np.uint32), ("material", np.int32)])
+assert HIT_DTYPE.itemsize == C.sizeof(Hit) == 16
+
+
 def array(struct, items):
     """Build a ctypes array of `struct` from a list of structs."""
     arr = (struct * max(len(items), 1))()

@@ -6,8 +6,12 @@
 //
 //   rt_cli [--width 1280] [--height 720] [--depth 0] [--time 0] [--frames 1]
 //          [--dt 0.016] [--scene shipped|spheres:N[:seed]|FILE.json] [--ppm out_%04d.ppm]
-//          [--pfm out_%04d.pfm] [--device 0] [--gpus N [--transport rccl|copy] [--block-rows 8]]
+//          [--pfm out_%04d.pfm] [--hits PREFIX] [--device 0] [--gpus N [--transport rccl|copy] [--block-rows 8]]
 //
+// --hits PREFIX also writes every frame's primary-hit buffers (rt_render_hits)
+// as three PFMs: PREFIX.hit.pfm (object index, t, shadow mask, as floats),
+// PREFIX.normal.pfm and PREFIX.point.pfm (PREFIX may hold a %d for the frame
+// number). One GPU only.
 // --gpus N renders every frame on devices device..device+N-1 with
 // rt_render_multi (row blocks per GPU, RCCL gather to the first GPU).
 #include <chrono>
@@ -41,7 +45,7 @@ int main(int argc, char **argv) {
     int width = 1280, height = 720, depth = 0, frames = 1, device = 0;  // main.cpp:17-19
     int gpus = 1, block_rows = 8, transport = RT_MULTI_RCCL;
     float time0 = 0.0f, dt = 1.0f / 60.0f;
-    std::string scene = "shipped", ppm, pfm;
+    std::string scene = "shipped", ppm, pfm, hits;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -57,6 +61,7 @@ int main(int argc, char **argv) {
         else if (a == "--scene") scene = next();
         else if (a == "--ppm") ppm = next();
         else if (a == "--pfm") pfm = next();
+        else if (a == "--hits") hits = next();
         else if (a == "--device") device = std::atoi(next());
         else if (a == "--gpus") gpus = std::atoi(next());
         else if (a == "--block-rows") block_rows = std::atoi(next());
@@ -64,11 +69,12 @@ int main(int argc, char **argv) {
         else {
             std::fprintf(stderr, "usage: rt_cli [--width W] [--height H] [--depth D] [--time T] [--frames K] "
                                  "[--dt S] [--scene shipped|spheres:N[:seed]|FILE.json] [--ppm PAT] [--pfm PAT] "
-                                 "[--device I] [--gpus N] [--transport rccl|copy] [--block-rows B]\n");
+                                 "[--hits PREFIX] [--device I] [--gpus N] [--transport rccl|copy] [--block-rows B]\n");
             return 2;
         }
     }
     if (gpus < 1) { std::fprintf(stderr, "rt_cli: --gpus must be >= 1\n"); return 2; }
+    if (!hits.empty() && gpus > 1) { std::fprintf(stderr, "rt_cli: --hits renders on one GPU (not with --gpus above 1)\n"); return 2; }
     std::vector<rt_context *> ctxs(gpus, nullptr);
     for (int g = 0; g < gpus; ++g)
         if (rt_create(device + g, &ctxs[g]) != RT_OK) return fail("rt_create");
@@ -158,6 +164,25 @@ int main(int argc, char **argv) {
             return fail("rt_write_ppm");
         if (!pfm.empty() && rt_write_pfm(frame_name(pfm, k).c_str(), frame.data(), width, height) != RT_OK)
             return fail("rt_write_pfm");
+        if (!hits.empty()) {
+            const size_t n_px = static_cast<size_t>(width) * height;
+            std::vector<rt_hit> rec(n_px);
+            std::vector<float> nrm(n_px * 4), pnt(n_px * 4), enc(n_px * 4);
+            if (rt_render_hits(ctx, scs[0], has_cam ? &cam : nullptr, t, width, height, 0, height, RT_HITS_SHADOW,
+                               rec.data(), nrm.data(), pnt.data(), 0, nullptr) != RT_OK)
+                return fail("rt_render_hits");
+            for (size_t i = 0; i < n_px; ++i) {  // (object, t, shadow mask) as floats
+                enc[4 * i] = static_cast<float>(rec[i].object);
+                enc[4 * i + 1] = rec[i].t;
+                enc[4 * i + 2] = static_cast<float>(rec[i].shadow);
+                enc[4 * i + 3] = 0.0f;
+            }
+            const std::string prefix = frame_name(hits, k);
+            if (rt_write_pfm((prefix + ".hit.pfm").c_str(), enc.data(), width, height) != RT_OK ||
+                rt_write_pfm((prefix + ".normal.pfm").c_str(), nrm.data(), width, height) != RT_OK ||
+                rt_write_pfm((prefix + ".point.pfm").c_str(), pnt.data(), width, height) != RT_OK)
+                return fail("rt_write_pfm");
+        }
     }
     rt_multi_destroy(group);
     for (int g = 0; g < gpus; ++g) {

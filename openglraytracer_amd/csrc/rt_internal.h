@@ -568,6 +568,22 @@ size_t lds_bytes(const SceneLayout &L, bool lean = false);
 int queued_views(const SceneLayout &L, int max_depth);
 // Self-test of the kernel argument block on the context's stream (rt_create).
 int check_kernarg_block(hipStream_t stream);
+// The primary-hit kernel's second argument (rt_render_hits*, rt_pick): the
+// planes it writes, one 16-B record per pixel of the launch's rows each
+// (nullptr: the plane is not wanted), and the RT_HITS_* flags. The launch
+// itself travels in LaunchParams as for a render (one view, rows
+// [row_begin, row_begin + n_rows), no shards); LaunchParams::out is not read.
+struct HitTargets {
+    int4 *hits;       // rt_hit: object, t, shadow mask, material
+    float4 *normals;  // (n, 0); a miss (0, 0, 0, 0)
+    float4 *points;   // (p, 0); a miss (0, 0, 0, 0)
+    int32_t flags;
+    int32_t pad;
+};
+static_assert(sizeof(HitTargets) == 32 && sizeof(LaunchParams) + sizeof(HitTargets) <= 6144, "kernel argument block");
+// Launches hits_kernel (not a row of the render table: select_kernel and
+// find_kernel do not know it), tiled, on `stream`.
+hipError_t launch_hits(LaunchParams &p, const HitTargets &o, hipStream_t stream);
 
 // rt_api.cpp
 void set_error(const std::string &msg);
@@ -620,6 +636,8 @@ struct rt_context {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float4 *staging = nullptr;  // device buffer for host-destination renders
     size_t staging_px = 0;
+    float4 *hits_staging = nullptr;  // the same for rt_render_hits*: three planes of hits_staging_px records
+    size_t hits_staging_px = 0;
     bool timed = false;
     int culling = 1;  // RT_OPT_CULLING
     int timing = 1;   // RT_OPT_TIMING

@@ -2379,6 +2379,167 @@ __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchPar
     }
 }
 
+// ---- primary-hit buffers (rt_render_hits*, rt_pick) ------------------------
+// What trace0 computes on the way to a pixel's colour, kept instead of
+// shaded: the closest hit (closest<true>), its collision record
+// (resolve<true>) and, with RT_HITS_SHADOW, the answer of every light's
+// shadow query (:807-819) as a bit mask. No shading math.
+//
+// The shadow bits cover every light, and every lane with a hit asks
+// (need = hit): phong_impl casts a shadow ray only where the light's term can
+// change the colour, which is a statement about the colour, not about the
+// occlusion. What the culling structures of a shadow query are built from
+// (rt_scene.cpp, rt_cull.h, and the animate kernel's phases, rt_anim.hip):
+//  * per light, dead ones included: BoxRec::light_inside (light_inside_box,
+//    bits j < 32), the separating planes (box_light_plane, n_boxes x n_lights)
+//    and the ShadowCone table (n_lights x n_spheres) — all geometry of the
+//    light's position alone;
+//  * per live light only: the LDS direction masks and their box bits, indexed
+//    by the live-slot counter (build_direction_masks skips dead lights), the
+//    wide masks and their candidate lists (depth >= 2, not read here), and the
+//    room flag (DeviceScene::room: every live light inside the one box — a
+//    dead light may be outside it; this kernel runs with S.room = 0 anyway).
+// A live light's query is phong_impl's: the live-slot counter, the
+// direction_mask lookup where the scene has LDS masks, else the per-wave cone
+// or the BVH walk, from p + 0.01 n along L - p. None of those structures
+// depends on which way the surface faces, so asking for back-facing lanes too
+// is covered by the same margins. A dead light has no mask slot, so its query
+// runs on a copy of the scene with cull = 0 and no planes: occluded_impl then
+// tests every box (without the slab pre-test; light_inside, valid for every
+// light, still shortcuts) and every sphere exactly.
+__device__ __forceinline__ void hits_wave_tile(const LaunchParams &p, const HitTargets &o, Scene S,
+                                               const FrameView &V, int wx, int wy, const Pixel &px, const Ray &ray) {
+    S.cull = V.cull;
+    S.room = 0;
+    S.cam_terms = 1;
+    if (!S.cull) S.cbplane = nullptr;  // (culling off: every box tested)
+    if (!wave_any(px.active)) return;
+    const bool active = px.active;
+    S.tx0 = wx * 8;
+    S.tx1 = S.tx0 + 7;
+    S.ty0 = output_row(p, p.slice_begin + wy * 8);  // (unsharded: 8 consecutive frame rows)
+    S.ty1 = S.ty0 + 7;
+    // the record's index in each plane: px.local_row < n_rows, px.x < width for an active lane
+    const size_t at = static_cast<size_t>(static_cast<uint32_t>(px.local_row) * static_cast<uint32_t>(p.width) +
+                                          static_cast<uint32_t>(px.x));
+    const Hit h = closest<true>(S, ray, active);
+    const bool hit = active && h.obj >= 0;
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!wave_any(hit)) {  // per-wave early out: misses
+        if (active) {
+            if (o.hits) o.hits[at] = make_int4(-1, 0, 0, -1);
+            if (o.normals) o.normals[at] = zero;
+            if (o.points) o.points[at] = zero;
+        }
+        return;
+    }
+    const Collision c = resolve<true>(S, ray, h, hit);
+    uint32_t shadow = 0u;
+    if ((o.flags & RT_HITS_SHADOW) != 0 && o.hits) {
+        Scene U = S;  // a dead light's query: nothing culled
+        U.cull = 0;
+        U.cbplane = nullptr;
+        const v3 start = add(c.p, muls(c.n, 0.01f));  // (:808)
+        int slot = -1;  // index among the live lights (direction masks)
+        for (int j = 0; j < S.nl; ++j) {
+            const LightRec L = cload(S.clight + j);
+            const v3 lpos = mk(L.pos[0], L.pos[1], L.pos[2]);
+            const v3 sdir = sub(lpos, c.p);  // (:809)
+            bool shadowed;
+            if (L.dead != 0.0f) {
+                shadowed = occluded(U, start, sdir, c.p, lpos, j, 0, 0u, hit);
+            } else {
+                ++slot;
+                uint64_t smask = 0u;
+                if (S.dmask)
+                    smask = direction_mask(S.dmask + slot * 6 * S.dmask_n * S.dmask_n * S.dmask_bytes, S.dmask_n,
+                                           S.dmask_bytes, muls(sdir, -1.0f), S.ns + (S.dmask_box ? S.nb : 0));
+                shadowed = occluded(S, start, sdir, c.p, lpos, j, slot, smask, hit);
+            }
+            if (hit && shadowed) shadow |= 1u << j;
+        }
+    }
+    if (!active) return;
+    // one 16-B store per lane and plane: a wave tile's 8 pixels of a row are a 128-B line
+    if (o.hits)
+        o.hits[at] = hit ? make_int4(h.obj, __float_as_int(h.t), static_cast<int>(shadow), c.material)
+                         : make_int4(-1, 0, 0, -1);
+    if (o.normals) o.normals[at] = hit ? make_float4(c.n.x, c.n.y, c.n.z, 0.0f) : zero;
+    if (o.points) o.points[at] = hit ? make_float4(c.p.x, c.p.y, c.p.z, 0.0f) : zero;
+}
+
+// The tiled launch of the general depth-0 kernel, one view: render_kernel's
+// prologue (the scene blob into LDS, the host's frame constants or
+// frame_setup, one barrier, s_setprio around it) written out again, so that
+// no helper shared with render_kernel re-rolls the render kernels' register
+// allocation. Every scene feature is read at run time (kShape 0). Not a row
+// of kKernels: launch_hits runs it.
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RT_WAVES_PER_EU(0, 0))))
+void hits_kernel(LaunchParams p, HitTargets o) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds[];
+    __builtin_amdgcn_s_setprio(1);
+    const FrameView &V = p.view[0];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float4 *blob = static_cast<const float4 *>(p.scene);
+    const int tid = threadIdx.x;
+    float4 first = make_float4(0.0f, 0.0f, 0.0f, 0.0f), fc = first;
+    if (tid < p.layout.blob_units) first = blob[tid];
+    if (tid < p.n_frame_consts) fc = p.frame_consts[tid];
+    float4 *const views = lds + p.layout.blob_units;
+    float4 *sph_cam = views;
+    int4 *sph_px = reinterpret_cast<int4 *>(views + p.layout.n_spheres);
+    float4 *box_cam = reinterpret_cast<float4 *>(sph_px + p.layout.n_spheres);
+    const int own_wx = static_cast<int>(blockIdx.x) * kWavesX + wave % kWavesX;
+    const int own_wy = static_cast<int>(blockIdx.y) * kWavesY + wave / kWavesX;
+    const Pixel own = wave_pixel(p, own_wx, own_wy);
+    // (the camera rays while the staging loads are in flight)
+    const Ray own_ray = camera_ray(p, V, own.x, own.y, 0.0f, 0.0f);
+    if (tid < p.layout.blob_units) lds[tid] = first;
+    for (int i = tid + kThreads; i < p.layout.blob_units; i += kThreads) lds[i] = blob[i];
+    if (p.n_frame_consts > 0) {
+        if (tid < p.n_frame_consts) views[tid] = fc;
+    } else {
+        frame_setup(p, V, sph_cam, sph_px, box_cam);
+    }
+    __syncthreads();
+    __builtin_amdgcn_s_setprio(0);
+    const SceneLayout &L = p.layout;
+    Scene S;
+    S.sph = lds + L.off_spheres;
+    S.smeta = reinterpret_cast<const int4 *>(lds + L.off_smeta);
+    S.sph_cam = sph_cam;
+    S.sph_px = sph_px;
+    S.box = reinterpret_cast<const BoxRec *>(lds + L.off_boxes);
+    S.box_cam = box_cam;
+    S.mat = reinterpret_cast<const MatRec *>(lds + L.off_mats);
+    S.light = reinterpret_cast<const LightRec *>(lds + L.off_lights);
+    S.lm = reinterpret_cast<const LightMatRec *>(lds + L.off_lightmat);
+    S.bvh = lds + L.off_bvh;
+    S.blink = reinterpret_cast<const uint32_t *>(lds + L.off_blink);
+    S.cone = L.off_cone >= 0 ? reinterpret_cast<const ShadowCone *>(lds + L.off_cone) : nullptr;
+    S.dmask = L.off_dmask >= 0 ? reinterpret_cast<const char *>(lds + L.off_dmask) : nullptr;
+    S.dmask_n = L.dmask_n;
+    S.dmask_bytes = L.dmask_bytes;
+    S.dmask_box = L.dmask_box;
+    S.cbplane = L.off_bplane >= 0 ? (const __attribute__((address_space(4))) float4 *)(blob + L.off_bplane) : nullptr;
+    S.gmask = nullptr;  // (as at depth 0: no wide masks, candidate lists or origin-sphere lists)
+    S.gwords = 0;
+    S.glist = nullptr;
+    S.olist = nullptr;
+    S.cbox = (const __attribute__((address_space(4))) BoxRec *)(blob + L.off_boxes);
+    S.clight = (const __attribute__((address_space(4))) LightRec *)(blob + L.off_lights);
+#ifdef RT_UNIFORM_MAT
+    S.cmat = (const __attribute__((address_space(4))) MatRec *)(blob + L.off_mats);
+    S.clm = (const __attribute__((address_space(4))) LightMatRec *)(blob + L.off_lightmat);
+#endif
+    S.nbvh = L.n_bvh;
+    S.ns = L.n_spheres;
+    S.nb = L.n_boxes;
+    S.nl = L.n_lights;
+    S.nm = L.n_mats;
+    hits_wave_tile(p, o, S, V, own_wx, own_wy, own, own_ray);
+}
+
 // Resident work-groups per CU of a kernel at a dynamic LDS size (cached: the
 // occupancy query is host work).
 int groups_per_cu(const void *fn, size_t lds) {
@@ -2495,6 +2656,20 @@ size_t persistent_lds_bytes(const LaunchParams &p) {
 }
 
 }  // namespace
+
+hipError_t launch_hits(LaunchParams &p, const HitTargets &o, hipStream_t stream) {
+    // one slice, one work-group per 16x16 tile of the launch's rows, no queue counters
+    p.slice_begin = 0;
+    p.slice_rows = p.n_rows;
+    p.sched = nullptr;
+    HitTargets targets = o;
+    void *args[] = {&p, &targets};
+    const dim3 grid((p.width + kTileX - 1) / kTileX, (p.n_rows + kTileY - 1) / kTileY, 1);
+    const hipError_t e = hipLaunchKernel(reinterpret_cast<const void *>(&hits_kernel), grid, dim3(kThreads), args,
+                                         lds_bytes(p.layout), stream);
+    (void)hipGetLastError();  // (e is the launch's own status; no sticky error for a later check)
+    return e;
+}
 
 int scene_shape(const SceneLayout &L, const LaunchHost &h, int max_depth) {
     if (!h.shape_cull) return 0;  // culling off for a view (or RT_OPT_SCENE_SHAPES 0)
@@ -2654,6 +2829,8 @@ int check_kernarg_block(hipStream_t stream) {
 hipError_t allow_large_lds(size_t bytes) {
     for (const KernelRow &row : kKernels)
         (void)hipFuncSetAttribute(row.fn(), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hits_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              static_cast<int>(bytes));
     (void)hipGetLastError();  // do not leak a sticky error into the next launch check
     return hipSuccess;
 }

@@ -61,6 +61,8 @@ def kernel_name(mangled):
     m = re.search(r"animate_kernelILb([01])E", mangled)
     if m:  # the instance with the sphere phases (rt_anim.hip), or the box phases alone
         return "animate_kernel<%s>" % ("true" if m.group(1) == "1" else "false")
+    if re.search(r"\d+hits_kernelE", mangled):  # the primary-hit kernel (rt_kernel.hip; not a row of the render table)
+        return "hits_kernel"
     return mangled
 
 
@@ -101,7 +103,7 @@ def resources(so):
     for r in out.values():
         if "vgpr" in r:
             r["waves_per_simd"] = min(8, 512 // max(8, -(-r["vgpr"] // 8) * 8))
-    return {k: v for k, v in out.items() if k.startswith(("render_kernel", "animate_kernel"))}
+    return {k: v for k, v in out.items() if k.startswith(("render_kernel", "animate_kernel", "hits_kernel"))}
 
 
 def texts(so):
@@ -171,6 +173,7 @@ TABLE = [
     ("depth 0, Monte-Carlo, config 5", "render_kernel<0,true,false,18>"),
     ("depth 0, general", "render_kernel<0,false,false>"),
     ("depth 0, Monte-Carlo, general", "render_kernel<0,true,false>"),
+    ("the primary-hit kernel (rt_render_hits, rt_pick: the general depth-0 kernel's shape, no shading)", "hits_kernel"),
     ("depth 1 (config 1)", "render_kernel<1,false,false>"),
     ("depth 2, config 3 (room, wide masks, origin lists)", "render_kernel<2,false,false,48>"),
     ("depth 2, general", "render_kernel<2,false,false>"),
