@@ -508,7 +508,8 @@ int rt_multi_last_ms(rt_multi *m, float *kernel_ms, float *gather_ms, float *ass
  * culling on; the mask width as a constant); at depth >= 2 without
  * Monte-Carlo, wide masks with their candidate lists and origin-sphere lists
  * (33-256 spheres, culling on); either with or without the room (exactly one
- * translate-only box holding every live light). 0: every render runs the
+ * translate-only box holding every live light; its whole-frame depth-0
+ * renders from inside it: RT_OPT_ROOM_FAST). 0: every render runs the
  * general kernel. Output is identical. */
 #define RT_OPT_SCENE_SHAPES 8
 /* RT_OPT_LAUNCH_SHAPES (default 1): a depth-0 render that runs a scene-shape
@@ -540,6 +541,15 @@ int rt_multi_last_ms(rt_multi *m, float *kernel_ms, float *gather_ms, float *ass
  * 0: every launch reads the offsets at run time; the scenes' blobs are the
  * same. Output is identical. */
 #define RT_OPT_FIXED_LAYOUT 11
+/* RT_OPT_ROOM_FAST (default 1): a depth-0 whole-frame float4 render
+ * (RT_OPT_LAUNCH_SHAPES) of a room scene (RT_OPT_SCENE_SHAPES) whose room is
+ * placed by a translation alone, with a normal matrix that leaves the face
+ * axes as they are, and whose cameras all stand strictly inside it takes the
+ * primary box hit
+ * without the products by those matrices. A launch outside that proof, and
+ * every launch with 0, runs the room kernels of the general launch shape.
+ * Output is identical. */
+#define RT_OPT_ROOM_FAST 12
 /* (option 6, a tolerance tier that summed the recursion's colours forward
  * instead of mixing them on the way back up, measured even with the exact
  * walk and was removed: DESIGN.md §3.) */

@@ -350,6 +350,13 @@ class Context:
         way."""
         _check(lib().rt_context_set(self._h, abi.RT_OPT_FIXED_LAYOUT, 1 if on else 0))
 
+    def set_room_fast(self, on):
+        """RT_OPT_ROOM_FAST: a plain depth-0 launch of a room scene inside
+        the host's proof (identity matrices, cameras strictly inside) takes
+        the primary box hit without the matrix products (include/rt.h).
+        Output identical either way."""
+        _check(lib().rt_context_set(self._h, abi.RT_OPT_ROOM_FAST, 1 if on else 0))
+
     def set_output(self, fmt):
         """RT_OPT_OUTPUT: abi.RT_OUTPUT_RGBA32F (float4 per pixel),
         abi.RT_OUTPUT_RGBA8 (the shipped GL_RGBA8 surface, 4 bytes per pixel)

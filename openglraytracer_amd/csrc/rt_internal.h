@@ -7,8 +7,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -281,6 +283,10 @@ struct LaunchParams {
     // Rows [slice_begin, slice_begin + slice_rows) of the launch's local rows
     // (the whole launch when slice_rows = 0).
     int32_t slice_begin, slice_rows;
+    // 1: the launch's room proof holds (LaunchHost::room_fast, kRoomFast): the
+    // general depth-0 colour kernels take the room fast path. (In the padding
+    // ahead of the pointers: the block's size and every other offset stand.)
+    int32_t room_fast;
     // > kMaxViews views (render_kernel<D, false, true>): n_views FrameViews
     // and n_views x n_frame_consts records in device memory; nullptr: the
     // arrays above
@@ -304,6 +310,11 @@ struct LaunchHost {
     // so the kernels may take the scene's shape (scene_shape)
     int32_t shape_cull;
     int32_t scene_room;  // every scene of the launch is a room (DeviceScene::room)
+    // The room proof of the launch (kRoomFast): every scene's record passes
+    // room_record_identity (DeviceScene::room_fast), every view's host-made
+    // box record room_view_inside, and RT_OPT_ROOM_FAST is on. launch_shape
+    // gives a room scene the plain launch only with it.
+    int32_t room_fast;
     // RT_OPT_LAUNCH_SHAPES: the depth-0 shaped kernels may take the launch's
     // shape (launch_shape)
     int32_t shape_launch;
@@ -334,6 +345,65 @@ constexpr int kShapeWide = 32;
 // kernel takes its table addresses from the class instead of reading
 // LaunchParams::layout per wave tile. Never with RT_OPT_FIXED_LAYOUT 0.
 constexpr int kShapeFixed = 64;
+// The room fast path (rt_kernel.hip closest_impl / resolve_impl<true, true>):
+// the kernels of the room shape on a plain launch (kShapeRoom, kLaunchPlain;
+// depth 0, no accumulation) take the primary box hit without the products by
+// the box's identity matrices. launch_shape gives a room scene the plain
+// launch only with the host's proof (LaunchHost::room_fast), so no kernel is
+// added; a launch without it runs the room kernels of the general launch.
+// The general depth-0 colour kernels (RT_OPT_SCENE_SHAPES 0, or a scene
+// without LDS masks) read the proof's answer from LaunchParams::room_fast.
+// Which launch took the path: kernel_takes_room_fast below.
+// (-DRT_ROOM_FAST=0: a timing build whose plain room kernels keep the general
+// code and whose launches do not ask for the proof, tools/ablate.sh flags)
+#ifndef RT_ROOM_FAST
+#define RT_ROOM_FAST 1
+#endif
+constexpr bool kRoomFast = RT_ROOM_FAST != 0;
+// The proof's scene half, on the room's record. The 3x3 blocks of w2l and l2w
+// are the identity (1.0f, and zeros of either sign: with the view half no
+// zero's sign in them reaches a result, DESIGN.md §3 "Arithmetic"), their
+// translation columns are finite (w2l_w0 then holds zeros), and the normal
+// matrix takes each of the six signed face axes the kernel forms (resolve_impl:
+// the axis, or the axis times -1.0f) to the vector the fast path writes: the
+// sign at the face's place and +0 elsewhere, bit for bit. The signs of the
+// normal matrix' zeros decide that last part (the reference's own transform
+// chain leaves -0 in places), so it is evaluated here as the kernel does.
+inline bool room_record_identity(const BoxRec &b) {
+    const auto bits = [](float f) {
+        uint32_t u;
+        std::memcpy(&u, &f, sizeof u);
+        return u;
+    };
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) {
+            const float want = r == c ? 1.0f : 0.0f;
+            if (b.w2l[r * 4 + c] != want || b.l2w[r * 4 + c] != want) return false;
+        }
+        if (!std::isfinite(b.w2l[r * 4 + 3]) || !std::isfinite(b.l2w[r * 4 + 3]) || b.w2l_w0[r] != 0.0f) return false;
+    }
+    for (int face = 0; face < 3; ++face)
+        for (const float sign : {1.0f, -1.0f}) {
+            float n[3] = {face == 0 ? 1.0f : 0.0f, face == 1 ? 1.0f : 0.0f, face == 2 ? 1.0f : 0.0f};
+            if (sign < 0.0f)
+                for (float &x : n) x = x * -1.0f;
+            for (int r = 0; r < 3; ++r) {
+                const float *N = b.nrm + 3 * r;
+                const float v = N[0] * n[0] + N[1] * n[1] + N[2] * n[2];
+                if (bits(v) != bits(r == face ? sign : 0.0f)) return false;
+            }
+        }
+    return true;
+}
+// The proof's view half, on the view's own record of the box (the kernel's
+// box_cam: the box-local camera origin, w = 1 when strictly inside): inside,
+// finite, and no component a negative zero.
+inline bool room_view_inside(const float4 &box_cam) {
+    const float v[3] = {box_cam.x, box_cam.y, box_cam.z};
+    for (const float f : v)
+        if (!std::isfinite(f) || (f == 0.0f && std::signbit(f))) return false;
+    return box_cam.w == 1.0f;
+}
 // Layout classes of the LDS-mask scenes. A class is one box or several; inside
 // it the tables a depth-0 shaped kernel reads sit at offsets that are a
 // function of the class and the sphere count alone: first the tables whose
@@ -508,6 +578,7 @@ struct DeviceScene {
     // 1: the one box is a room: translate-only, every live light strictly
     // inside it (the shadow queries' box shortcut always applies; kShapeRoom)
     int32_t room = 0;
+    int32_t room_fast = 0;  // a room whose record passes room_record_identity (kRoomFast)
 };
 
 // rt_scene.cpp: every view's per-frame constants on the host, bit-identical
@@ -556,6 +627,12 @@ struct KernelChoice {
     bool candidate;
 };
 bool select_kernel(const LaunchParams &p, const LaunchHost &h, int max_depth, KernelChoice &c);
+// The launch of row k with parameters p takes the room fast path.
+inline bool kernel_takes_room_fast(const KernelKey &k, const LaunchParams &p) {
+    if (!kRoomFast || k.depth != 0 || k.accum) return false;
+    if (k.shape == 0) return p.room_fast != 0;
+    return (k.shape & kShapeRoom) != 0 && (k.launch & kLaunchPlain) != 0;
+}
 // Launches the row select_kernel names (`ran`: its key). Clears p.sched when
 // the launch does not use the queued distribution (so the caller knows
 // whether the counter slot is in use).
@@ -648,6 +725,8 @@ struct rt_context {
     int launch_shapes = 1;  // RT_OPT_LAUNCH_SHAPES
     int persistent0 = 1;  // RT_OPT_PERSISTENT0
     int fixed_layout = 1;  // RT_OPT_FIXED_LAYOUT
+    int room_fast = 1;  // RT_OPT_ROOM_FAST
+    bool last_room_fast = false;  // the last launch took the room fast path (rt_debug_last_room_fast)
     // device-side view batches (> kMaxViews views): per slot a device buffer,
     // its pinned host staging and an event after the last launch that read it
     void *batch_dev[rtamd::kBatchSlots] = {};

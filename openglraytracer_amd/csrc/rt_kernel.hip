@@ -392,6 +392,7 @@ struct Scene {
     int ns, nb, nl, nm, nbvh;
     int cull;
     int room;  // the one box is a room (kShapeRoom): its shadow shortcut always applies
+    int room_fast;  // LaunchParams::room_fast, where the kernel reads it at run time (kRoomFastUniform)
     int tx0, tx1, ty0, ty1;  // this wave's pixel rectangle (frame coordinates)
 };
 
@@ -456,6 +457,10 @@ __device__ __forceinline__ bool strictly_inside(const BoxRec &b, v3 rs) {
            rs.z < b.maxs[2];
 }
 __device__ __forceinline__ bool not_nan(v3 v) { return v.x == v.x && v.y == v.y && v.z == v.z; }
+__device__ __forceinline__ bool finite3(v3 v) {
+    const float inf = __builtin_inff();
+    return fabsf(v.x) < inf && fabsf(v.y) < inf && fabsf(v.z) < inf;
+}
 // Inside the box the slab's t2 on an axis is the exit boundary chosen by the
 // sign of the direction: max((mins-s)/d, (maxs-s)/d) with one division. For
 // d = +-0 the sign bit picks the +inf quotient, exactly as max() does.
@@ -688,11 +693,31 @@ __device__ __forceinline__ int direction_texel(int n, v3 u);
 
 // get_closest_collision (:738-782). Called with all lanes active. origin:
 // the sphere slot a secondary ray starts on (-1: the camera or a box).
-template <bool kPrimary>
+// The room fast path (kRoom: kRoomFastShape in the plain depth-0 room
+// kernels, a constant; kRoomFastUniform in the general depth-0 colour kernels,
+// which read the launch's answer as they read every other feature: one
+// scalar branch). The host proved the one box's matrices the identity, as far
+// as a result can tell, and the camera strictly inside it (rt_internal.h
+// room_record_identity, room_view_inside), so the camera ray's direction is
+// the box-local one as it stands and the ray leaves the box: DESIGN.md §3
+// "Arithmetic" shows the Hit and the Collision bit for bit those of the
+// general code below. A direction with a component that is not finite has a
+// NaN in two rows or more of the general code's product (0 x inf, 0 x NaN),
+// so every slab quotient there is a NaN or a zero and the box is missed.
+enum { kRoomGeneral = 0, kRoomFastShape = 1, kRoomFastUniform = 2 };
+template <bool kPrimary, int kRoom = kRoomGeneral>
 __device__ __forceinline__ Hit closest_impl(const Scene &S, const Ray &r, bool valid, int origin) {
+    static_assert(kPrimary || kRoom == kRoomGeneral, "the room fast path: camera rays");
     Hit h{10000.0f, -1, 0, 0};
     RT_STAT(kPrimary ? 0 : 1, valid);
     RT_STAT(kPrimary ? 13 : 2, (threadIdx.x & 63) == __builtin_ctzll(__ballot(1)));
+    if (kRoom == kRoomFastShape || (kRoom == kRoomFastUniform && S.room_fast != 0)) {
+        const BoxRec B = cload(S.cbox);
+        const float4 c = S.box_cam[0];
+        const v3 bnd = exits(B, mk(c.x, c.y, c.z), r.dir);
+        const float t = gmin(gmin(bnd.x, bnd.y), bnd.z);
+        if (finite3(r.dir) && closer(t, B.obj_index, h)) h = {t, B.obj_index, ~0, 1 | (box_face(t, bnd) << 1)};
+    } else
     for (int b = 0; b < S.nb; ++b) {
         const BoxRec B = cload(S.cbox + b);
         v3 rs;
@@ -841,10 +866,10 @@ __device__ __forceinline__ Hit closest_impl(const Scene &S, const Ray &r, bool v
     if (!valid) h.obj = -1;
     return h;
 }
-template <bool kPrimary>
+template <bool kPrimary, int kRoom = kRoomGeneral>
 __device__ __forceinline__ Hit closest(const Scene &S, const Ray &r, bool valid, int origin = -1) {
     RT_CYC(kPrimary ? kCycClosest1 : kCycClosest2);
-    const Hit h = closest_impl<kPrimary>(S, r, valid, origin);
+    const Hit h = closest_impl<kPrimary, kRoom>(S, r, valid, origin);
     RT_CYC_AFTER(kCycWalk, h.t);
     return h;
 }
@@ -1188,7 +1213,10 @@ struct Collision {
 // Build the collision record of the winning object (:628-637, :686-721).
 // A box's slab distances come with the hit (the closest-hit loop computed
 // them); its t is the slab test's intersection distance.
-template <bool kPrimary>
+// The room fast path (closest_impl): the box is the room, its record the scalar one;
+// the signed face axis is the normal and the local point plus the translation
+// the world point (identity products dropped, same bits).
+template <bool kPrimary, int kRoom = kRoomGeneral>
 __device__ __forceinline__ Collision resolve_impl(const Scene &S, const Ray &r, const Hit &h, bool valid) {
     Collision c;
     c.p = mk(0.0f, 0.0f, 0.0f);
@@ -1204,6 +1232,17 @@ __device__ __forceinline__ Collision resolve_impl(const Scene &S, const Ray &r, 
         c.n = normalize(sub(c.p, pos));
         c.inside = h.info & 1;
         if (c.inside) c.n = muls(c.n, -1.0f);  // leaving the sphere: flip (:634-637)
+    } else if (kRoom == kRoomFastShape || (kRoom == kRoomFastUniform && S.room_fast != 0)) {
+        const BoxRec B = cload(S.cbox);
+        c.material = B.material;
+        const float4 bc = S.box_cam[0];
+        c.inside = h.info & 1;
+        const int face = h.info >> 1;  // box_face, decided in the scan
+        // (room_record_identity: the normal matrix takes the signed axis to this)
+        const float s = comp(r.dir, face) > 0.0f ? -1.0f : 1.0f;
+        c.n = mk(face == 0 ? s : 0.0f, face == 1 ? s : 0.0f, face == 2 ? s : 0.0f);
+        const v3 lp = add(mk(bc.x, bc.y, bc.z), muls(r.dir, h.t));
+        c.p = mk(lp.x + B.l2w[3], lp.y + B.l2w[7], lp.z + B.l2w[11]);
     } else {
         const BoxRec &B = S.box[~h.slot];
         c.material = B.material;
@@ -1227,10 +1266,10 @@ __device__ __forceinline__ Collision resolve_impl(const Scene &S, const Ray &r, 
     }
     return c;
 }
-template <bool kPrimary>
+template <bool kPrimary, int kRoom = kRoomGeneral>
 __device__ __forceinline__ Collision resolve(const Scene &S, const Ray &r, const Hit &h, bool valid) {
     RT_CYC(kCycResolve);
-    const Collision c = resolve_impl<kPrimary>(S, r, h, valid);
+    const Collision c = resolve_impl<kPrimary, kRoom>(S, r, h, valid);
     RT_CYC_AFTER(kCycWalk, c.p.x);
     return c;
 }
@@ -1419,14 +1458,15 @@ __device__ __forceinline__ v3 phong(const Scene &S, const Ray &r, const Collisio
 // pending refraction ray, 24 B, only where both children exist) indexed by
 // the lane's own level, which the compiler keeps in scratch (Frames). Lanes
 // whose tree is finished ride along with valid = false.
+template <int kRoom = kRoomGeneral>
 __device__ __forceinline__ v3 trace0(const Scene &S, const Ray &r, bool valid) {
     const v3 black = mk(0.0f, 0.0f, 0.0f);
     RT_PHASE(2);
-    const Hit h = closest<true>(S, r, valid);
+    const Hit h = closest<true, kRoom>(S, r, valid);
     RT_PHASE(3);
     const bool hit = valid && h.obj >= 0;
     if (!wave_any(hit)) return black;  // per-wave early out
-    const Collision c = resolve<true>(S, r, h, hit);
+    const Collision c = resolve<true, kRoom>(S, r, h, hit);
     RT_PHASE(4);
 #ifdef RT_ABLATE_PHONG
     const v3 col = add(c.p, c.n);
@@ -1942,7 +1982,16 @@ __device__ __forceinline__ void render_wave_tile(const LaunchParams &p, Scene S,
             trace_tree<kDepth>(S, ray, active, [&](v3 col) { store_pixel(p, z, idx, col); });
             return;
         }
-        const v3 col = trace0(S, ray, active);
+        // the room fast path: the room shape on a plain launch, whose room
+        // proof the host made (launch_shape; rt_internal.h kRoomFast), and the
+        // general kernel, which reads the proof's answer from the launch. Never
+        // the Monte-Carlo depth-0 kernels (no plain launch accumulates; their
+        // own A/B was not made), the primary-hit kernel or a recursive one.
+        constexpr int kRoom = !kRoomFast ? kRoomGeneral
+                              : kPlain && (kShape & kShapeRoom) != 0 ? kRoomFastShape
+                              : kShape == 0 ? kRoomFastUniform : kRoomGeneral;
+        if constexpr (kRoom == kRoomFastUniform) S.room_fast = p.room_fast;
+        const v3 col = trace0<kRoom>(S, ray, active);
 #endif
         RT_CYC_AFTER(kCycStore, col.x);
         if (active) store_pixel<kLaunch>(p, z, idx, col);
@@ -2715,9 +2764,11 @@ int launch_shape(const LaunchParams &p, const LaunchHost &h, int max_depth, int 
     if (!h.shape_launch || max_depth != 0 || p.spp > 0) return 0;  // (RT_OPT_LAUNCH_SHAPES 0, deeper, Monte-Carlo)
     const int slice_rows = p.slice_rows > 0 ? p.slice_rows : p.n_rows;  // (launch_render: 0 = the whole launch)
     const int slice_begin = p.slice_rows > 0 ? p.slice_begin : 0;
+    // a room's plain kernels take the room fast path: only with its proof
+    const bool room_ok = !kRoomFast || !(h.scene_room && p.layout.n_boxes == 1) || h.room_fast;
     const bool plain = p.n_shards <= 0 && p.row_begin == 0 && p.n_rows == p.height && slice_begin == 0 &&
                        slice_rows == p.n_rows && p.out_format == RT_OUTPUT_RGBA32F && p.cam_short == 1 &&
-                       p.n_frame_consts > 0 && p.width >= 2 && p.height >= 2;
+                       p.n_frame_consts > 0 && p.width >= 2 && p.height >= 2 && room_ok;
     return plain ? kLaunchPlain : 0;
 }
 

@@ -1396,6 +1396,7 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     ds.room = boxes.size() == 1 && boxes[0].translate_only;
     for (int j = 0; j < n_lights && ds.room; ++j)
         if (lrec[j].dead == 0.0f && (j >= 32 || !((boxes[0].light_inside >> j) & 1u))) ds.room = 0;
+    ds.room_fast = ds.room && room_record_identity(boxes[0]);
     lay.n_mats = n_mats;
     lay.n_lights = n_lights;
     blob.assign(static_cast<size_t>(off > 0 ? off : 1), float4{0, 0, 0, 0});
@@ -1555,7 +1556,7 @@ int anim_plan(const char *who_c, const rt_object *base, const rt_object_anim *an
     // room): a box without channels keeps the host's record (the kernel leaves
     // it alone), so build_scene's decision stands; a moving box never claims it.
     const bool static_room = L.n_boxes == 1 && !box_moves;
-    if (!static_room) ds.room = 0;
+    if (!static_room) ds.room = ds.room_fast = 0;
     // the kernel's static table
     AnimTable T{};
     T.n_boxes = static_room ? 0 : L.n_boxes;
