@@ -89,6 +89,7 @@ def lib():
             "rt_debug_anim_validate": ([vp, vp, vp, i, vp, i, vp, i, i, i], i),
             "rt_debug_anim_host_blob": ([vp, vp, vp, i, vp, i, vp, i, f, vp, C.c_longlong, vp], C.c_longlong),
             "rt_debug_select_kernel": ([vp, i, vp], i), "rt_debug_last_kernel": ([vp, vp], i),
+            "rt_debug_norm_proof": ([vp, i, vp, i, vp, i, vp, i, i, vp, vp], i),
             "rt_render_hits_view": ([vp, vp, vp, i, i, i, i, i, vp, vp, vp, i, vp], i),
             "rt_render_hits": ([vp, vp, vp, f, i, i, i, i, i, vp, vp, vp, i, vp], i),
             "rt_render_hits_animated": ([vp, vp, vp, f, i, i, i, i, i, vp, vp, vp, i, vp], i),
@@ -208,6 +209,19 @@ def last_kernel(ctx):
     out = (C.c_int32 * 6)()
     _check(lib().rt_debug_last_kernel(ctx.handle, out))
     return tuple(out)
+
+
+def norm_proof(objects, view, width, height, materials=None, lights=None):
+    """rt_debug_norm_proof (host only): ((scene half, view half, the build asks
+    launches for the proofs), (B, e2, gap)) of the range proofs that let the
+    room fast path take its inverse square roots without votes."""
+    mats = materials if materials is not None else reference_materials()
+    lights = lights if lights is not None else reference_lights()
+    oa, ma, la = (Object * len(objects))(*objects), (Material * len(mats))(*mats), (Light * len(lights))(*lights)
+    flags, terms = (C.c_int32 * 3)(), (C.c_double * 3)()
+    _check(lib().rt_debug_norm_proof(oa, len(objects), ma, len(mats), la, len(lights), C.byref(view), width, height,
+                                     flags, terms))
+    return tuple(flags), tuple(terms)
 
 
 def bench_objects(n_spheres, seed=0):

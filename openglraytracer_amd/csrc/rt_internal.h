@@ -360,6 +360,26 @@ constexpr int kShapeFixed = 64;
 #define RT_ROOM_FAST 1
 #endif
 constexpr bool kRoomFast = RT_ROOM_FAST != 0;
+// Round 18: the host also proves the operands of the path's inverse square
+// roots inside the short forms' ranges (norm_proof_scene, camera_norm_range
+// below), so the kernels that take the path call the short forms without their
+// per-wave range votes; the proofs join the launch's room proof
+// (LaunchHost::room_fast). (-DRT_NORM_PROOFS=0: a timing build in which no such
+// proof is asked for and the votes stay, tools/ablate.sh flags)
+#ifndef RT_NORM_PROOFS
+#define RT_NORM_PROOFS 1
+#endif
+constexpr bool kNormProofs = kRoomFast && RT_NORM_PROOFS != 0;
+// Timing builds that price an instruction of the persistent depth-0 kernel
+// (-DRT_PAD_SALU=n, -DRT_PAD_VALU=n, tools/ablate.sh flags; rt_kernel.hip
+// persistent_pad): n more scalar or vector adds per tile. DESIGN.md §3, round 18.
+#ifndef RT_PAD_SALU
+#define RT_PAD_SALU 0
+#endif
+#ifndef RT_PAD_VALU
+#define RT_PAD_VALU 0
+#endif
+constexpr int kPadSalu = RT_PAD_SALU, kPadValu = RT_PAD_VALU;
 // The proof's scene half, on the room's record. The 3x3 blocks of w2l and l2w
 // are the identity (1.0f, and zeros of either sign: with the view half no
 // zero's sign in them reaches a result, DESIGN.md §3 "Arithmetic"), their
@@ -403,6 +423,67 @@ inline bool room_view_inside(const float4 &box_cam) {
     for (const float f : v)
         if (!std::isfinite(f) || (f == 0.0f && std::signbit(f))) return false;
     return box_cam.w == 1.0f;
+}
+// The scene half of the norm proofs (kNormProofs; the view half is
+// rt_scene.cpp camera_norm_range). With it, at every primary hit of a room
+// launch the operands of normalize(sdir) (phong_impl) and of the sphere
+// normal (resolve_impl) lie inside inv_sqrt's [2^-96, 2^100] by twenty binades
+// or more, so the short forms need no vote. DESIGN.md §3 "Arithmetic" derives
+// the terms; in short, with B the largest |coordinate| of the room, the
+// spheres (centre +- radius) and the live lights, all in float64:
+//  * e2 = 2^-12 B^2 bounds | |p - C|^2 - r^2 | for the float32 hit point p of
+//    a sphere (C, r) from a camera inside the room: the discriminant's
+//    rounding, at most 2^-13.9 B^2, reaches the squared distance at most
+//    1.25-fold, grazing hits included;
+//  * gap = 2^-12 B: a wall's hit point is within 2^-20 B of its plane;
+//  * so: B <= 2^20; every |r| in [2^-20, 2^20] with r^2 >= 2 e2 (the normal's
+//    operand stays above e2 >= 2^-52); every live light at least gap from each
+//    wall plane, and its distance from C outside
+//    [sqrt(r^2 - e2) - gap, sqrt(r^2 + e2) + gap] for each sphere.
+// Then |sdir| >= gap - 2^-20 B >= 2^-33 and |sdir| <= 4 B <= 2^22.
+struct NormProof {
+    int32_t ok = 0;
+    double bound = 0.0, e2 = 0.0, gap = 0.0;
+};
+inline NormProof norm_proof_scene(const BoxRec &room, const SphereRec *sph, const SphereMeta *meta, int n_spheres,
+                                  const LightRec *lights, int n_lights) {
+    NormProof r;
+    double lo[3], hi[3], B = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = double(room.mins[k]) + double(room.l2w[4 * k + 3]);
+        hi[k] = double(room.maxs[k]) + double(room.l2w[4 * k + 3]);
+        B = std::fmax(B, std::fmax(std::fabs(lo[k]), std::fabs(hi[k])));
+    }
+    for (int s = 0; s < n_spheres; ++s) {
+        const double c[3] = {sph[s].cx, sph[s].cy, sph[s].cz}, rad = std::fabs(double(meta[s].radius));
+        for (const double x : c) B = std::fmax(B, std::fabs(x) + rad);
+    }
+    for (int j = 0; j < n_lights; ++j)
+        if (lights[j].dead == 0.0f)
+            for (const float x : lights[j].pos) B = std::fmax(B, std::fabs(double(x)));
+    if (!(B > 0.0 && B <= 0x1p20)) return r;  // (a NaN fails)
+    r.bound = B;
+    r.e2 = 0x1p-12 * B * B;
+    r.gap = 0x1p-12 * B;
+    for (int s = 0; s < n_spheres; ++s) {
+        const double rad = std::fabs(double(meta[s].radius));
+        // (the kernel's rr is the float product of the radius with itself)
+        if (!(rad >= 0x1p-20 && rad <= 0x1p20 && rad * rad >= 2.0 * r.e2 && double(sph[s].rr) >= 2.0 * r.e2)) return r;
+    }
+    for (int j = 0; j < n_lights; ++j) {
+        if (lights[j].dead != 0.0f) continue;
+        const double L[3] = {lights[j].pos[0], lights[j].pos[1], lights[j].pos[2]};
+        for (int k = 0; k < 3; ++k)
+            if (!(std::fabs(L[k] - lo[k]) >= r.gap && std::fabs(L[k] - hi[k]) >= r.gap)) return r;
+        for (int s = 0; s < n_spheres; ++s) {
+            const double dx = L[0] - sph[s].cx, dy = L[1] - sph[s].cy, dz = L[2] - sph[s].cz;
+            const double d = std::sqrt(dx * dx + dy * dy + dz * dz), rr = double(meta[s].radius) * double(meta[s].radius);
+            const bool outside = d >= std::sqrt(rr + r.e2) + r.gap, inside = d <= std::sqrt(rr - r.e2) - r.gap;
+            if (!outside && !inside) return r;
+        }
+    }
+    r.ok = 1;
+    return r;
 }
 // Layout classes of the LDS-mask scenes. A class is one box or several; inside
 // it the tables a depth-0 shaped kernel reads sit at offsets that are a
@@ -579,6 +660,10 @@ struct DeviceScene {
     // inside it (the shadow queries' box shortcut always applies; kShapeRoom)
     int32_t room = 0;
     int32_t room_fast = 0;  // a room whose record passes room_record_identity (kRoomFast)
+    // room_fast, and the scene passes norm_proof_scene (kNormProofs). A scene
+    // whose spheres the device moves (rt_anim) never claims it: the proof reads
+    // the spheres where the host put them.
+    NormProof norm;
 };
 
 // rt_scene.cpp: every view's per-frame constants on the host, bit-identical
@@ -596,6 +681,8 @@ int host_view_consts(const LaunchParams &p, const FrameView &V, const float4 *bl
 // A view's kernel-side constants (unprojection, proj for culling, origin,
 // cull flag); false if its perspective divisions may not take the short form.
 bool fill_view(const rt_context *ctx, const rt_view &view, int width, int height, FrameView &out);
+// rt_scene.cpp: the view half of the norm proofs (kNormProofs), see there
+bool camera_norm_range(const float M[16], int width, int height);
 
 // rt_camera.cpp: the reference orbit camera as llvmpipe evaluates it
 float gl_sin(float a);  // gallivm's polynomial sin / cos (run-time GLSL sin / cos)

@@ -171,6 +171,29 @@ __device__ __forceinline__ v3 normalize_unit(v3 a) {
     if (__builtin_expect(wave_all(near_one(d)), 1)) return muls(a, inv_sqrt_near_one(d));
     return muls(a, inv_sqrt(d));
 }
+// The same two without their votes, where the host proved the ranges for every
+// lane whose result is kept (rt_internal.h kNormProofs, DESIGN.md §3
+// "Arithmetic"). kProved: 0 the code above as it stands, 1 the proof holds for
+// every launch of the kernel (the plain room kernels), 2 `proved` says so (the
+// general depth-0 colour kernels: one scalar branch).
+template <int kProved>
+__device__ __forceinline__ v3 normalize_proved(v3 a, bool proved) {
+#ifndef RT_FAST_RSQ
+    if constexpr (kProved == 1) return muls(a, rcp_refined(sqrt_short(dot(a, a))).r);
+    if constexpr (kProved == 2)
+        if (proved) return muls(a, rcp_refined(sqrt_short(dot(a, a))).r);
+#endif
+    return normalize(a);
+}
+template <int kProved>
+__device__ __forceinline__ v3 normalize_unit_proved(v3 a, bool proved) {
+#ifndef RT_FAST_RSQ
+    if constexpr (kProved == 1) return muls(a, inv_sqrt_near_one(dot(a, a)));
+    if constexpr (kProved == 2)
+        if (proved) return muls(a, inv_sqrt_near_one(dot(a, a)));
+#endif
+    return normalize_unit(a);
+}
 __device__ __forceinline__ float gmin(float a, float b) { return a < b ? a : b; }
 __device__ __forceinline__ float gmax(float a, float b) { return a > b ? a : b; }
 __device__ __forceinline__ float comp(v3 v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }
@@ -716,7 +739,11 @@ __device__ __forceinline__ Hit closest_impl(const Scene &S, const Ray &r, bool v
         const float4 c = S.box_cam[0];
         const v3 bnd = exits(B, mk(c.x, c.y, c.z), r.dir);
         const float t = gmin(gmin(bnd.x, bnd.y), bnd.z);
-        if (finite3(r.dir) && closer(t, B.obj_index, h)) h = {t, B.obj_index, ~0, 1 | (box_face(t, bnd) << 1)};
+        // (kNormProofs: the launch's proof makes every pixel's direction finite,
+        // rt_scene.cpp camera_norm_range)
+        bool take = closer(t, B.obj_index, h);
+        if constexpr (!kNormProofs) take = finite3(r.dir) && take;
+        if (take) h = {t, B.obj_index, ~0, 1 | (box_face(t, bnd) << 1)};
     } else
     for (int b = 0; b < S.nb; ++b) {
         const BoxRec B = cload(S.cbox + b);
@@ -1229,7 +1256,12 @@ __device__ __forceinline__ Collision resolve_impl(const Scene &S, const Ray &r, 
         const v3 pos = mk(sp.x, sp.y, sp.z);
         c.material = S.smeta[h.slot].y;
         c.p = add(r.start, muls(r.dir, h.t));
-        c.n = normalize(sub(c.p, pos));
+        // (the room fast path: the squared distance of a hit point from its
+        // sphere's centre is the squared radius up to rounding, proved in range)
+        if constexpr (kNormProofs && kRoom != kRoomGeneral)
+            c.n = normalize_proved<kRoom>(sub(c.p, pos), kRoom == kRoomFastUniform && S.room_fast != 0);
+        else
+            c.n = normalize(sub(c.p, pos));
         c.inside = h.info & 1;
         if (c.inside) c.n = muls(c.n, -1.0f);  // leaving the sphere: flip (:634-637)
     } else if (kRoom == kRoomFastShape || (kRoom == kRoomFastUniform && S.room_fast != 0)) {
@@ -1342,15 +1374,27 @@ __device__ unsigned long long rt_phase_buf[kPhaseWaves * 16];
 // kUni (RT_UNIFORM_MAT probe, depth 0): every lane with a hit has material
 // `umat`, and the material and light x material records come by scalar
 // loads (SGPRs) instead of per-lane LDS gathers.
-template <bool kUni = false>
+// kRoom (the depth-0 colour kernels, closest_impl): on the room fast path the
+// inverse square roots take their forms without votes (kNormProofs: the
+// launch's proof covers every lane with a hit; a lane without one may compute
+// anything, its sums are never taken).
+template <bool kUni = false, int kRoom = kRoomGeneral>
 __device__ __forceinline__ v3 phong_impl(const Scene &S, const Ray &r, const Collision &c, bool valid, int umat = 0) {
 #if defined(RT_UNIFORM_MAT) && !defined(RT_UNIFORM_MAT_LM_ONLY)
     const MatRec m = kUni ? cload(S.cmat + umat) : S.mat[c.material];
 #else
     const MatRec &m = S.mat[c.material];
 #endif
+    // (normalize_proved's kProved takes kRoom's values as they stand)
+    static_assert(kRoomGeneral == 0 && kRoomFastShape == 1 && kRoomFastUniform == 2, "kProved: 0, 1, 2");
+    constexpr int kProved = kNormProofs ? kRoom : 0;
+    bool fast = kRoom == kRoomFastShape;
+    if constexpr (kRoom == kRoomFastUniform) fast = S.room_fast != 0;
     float4 dif = make_float4(0.0f, 0.0f, 0.0f, 0.0f), spe = dif;
-    const v3 view = normalize_unit(muls(r.dir, -1.0f));  // ray directions are unit vectors up to rounding
+    // ray directions are unit vectors up to rounding
+    v3 view;
+    if constexpr (kProved != 0) view = normalize_unit_proved<kProved>(muls(r.dir, -1.0f), fast);
+    else view = normalize_unit(muls(r.dir, -1.0f));
     int slot = -1;  // index among the live lights (direction masks)
     for (int j = 0; j < S.nl; ++j) {
         const LightRec L = cload(S.clight + j);
@@ -1367,7 +1411,9 @@ __device__ __forceinline__ v3 phong_impl(const Scene &S, const Ray &r, const Col
             ptexel = valid ? direction_texel(kGMaskTexels, muls(sdir, -1.0f)) : -1;
             if (ptexel >= 0) pre = S.glist[static_cast<size_t>(slot) * 6 * kGMaskTexels * kGMaskTexels + ptexel];
         }
-        const v3 ldir = normalize(sdir);
+        v3 ldir;
+        if constexpr (kProved != 0) ldir = normalize_proved<kProved>(sdir, fast);
+        else ldir = normalize(sdir);
         const float cos_theta = dot(ldir, c.n);
         // reflect(-ldir, n) needs dot(n, -ldir), which is -cos_theta (exact
         // negation, commuted products) except that an exactly-zero dot may
@@ -1375,7 +1421,9 @@ __device__ __forceinline__ v3 phong_impl(const Scene &S, const Ray &r, const Col
         // components of lref, which change cos_phi at most by the sign of a
         // zero, and max(cos_phi, 0) is +0 for both: the result is identical
         const v3 nl = muls(ldir, -1.0f);
-        const v3 lref = normalize_unit(sub(nl, muls(c.n, 2.0f * -cos_theta)));
+        v3 lref;
+        if constexpr (kProved != 0) lref = normalize_unit_proved<kProved>(sub(nl, muls(c.n, 2.0f * -cos_theta)), fast);
+        else lref = normalize_unit(sub(nl, muls(c.n, 2.0f * -cos_theta)));
         const float cos_phi = dot(view, lref);
 #ifdef RT_UNIFORM_MAT
         const LightMatRec q = kUni ? cload(S.clm + (umat * S.nl + j)) : S.lm[c.material * S.nl + j];
@@ -1438,9 +1486,10 @@ __device__ __forceinline__ v3 phong_impl(const Scene &S, const Ray &r, const Col
     const float pw = ((m.amb_sum[3] + dif.w) + spe.w) + m.emissive[3];
     return mk(px * pw, py * pw, pz * pw);
 }
+template <int kRoom = kRoomGeneral>
 __device__ __forceinline__ v3 phong(const Scene &S, const Ray &r, const Collision &c, bool valid) {
     RT_CYC(kCycPhong);
-    const v3 col = phong_impl(S, r, c, valid);
+    const v3 col = phong_impl<false, kRoom>(S, r, c, valid);
     RT_CYC_AFTER(kCycWalk, col.x);
     return col;
 }
@@ -1476,10 +1525,10 @@ __device__ __forceinline__ v3 trace0(const Scene &S, const Ray &r, bool valid) {
     const uint64_t hb = wave_ballot(hit);
     const int umat = __builtin_amdgcn_readlane(c.material, static_cast<int>(__builtin_ctzll(hb)));
     v3 col;
-    if (wave_all(!hit || c.material == umat)) col = phong_impl<true>(S, r, c, hit, umat);
-    else col = phong(S, r, c, hit);
+    if (wave_all(!hit || c.material == umat)) col = phong_impl<true, kRoom>(S, r, c, hit, umat);
+    else col = phong<kRoom>(S, r, c, hit);
 #else
-    const v3 col = phong(S, r, c, hit);
+    const v3 col = phong<kRoom>(S, r, c, hit);
 #endif
     return sel(hit, col, black);
 }
@@ -1845,7 +1894,20 @@ __device__ __forceinline__ Pixel wave_pixel(const LaunchParams &p, int wx, int w
 
 // Camera ray through pixel (x, y) offset by (jx, jy) (:377-392); jx = jy = 0
 // for the reference's one ray per pixel (float(x - hw) + 0.0f is exact).
-template <int kLaunch = 0>
+// Which room path a colour kernel's instance takes (render_wave_tile says why),
+// and whether its camera rays are normalised under the launch's proof: the
+// plain room kernels' (a constant; the general kernels keep the vote there).
+constexpr int room_path(int depth, bool accum, int shape, int launch) {
+    return !kRoomFast || depth != 0 || accum ? kRoomGeneral
+           : (launch & kLaunchPlain) != 0 && (shape & kShapeRoom) != 0 ? kRoomFastShape
+           : shape == 0 ? kRoomFastUniform : kRoomGeneral;
+}
+constexpr bool kCameraProved(int depth, bool accum, int shape, int launch) {
+    return kNormProofs && room_path(depth, accum, shape, launch) == kRoomFastShape;
+}
+// kProved: the launch's proof covers |e3 - s3|^2 at every pixel of the frame
+// (rt_scene.cpp camera_norm_range), so the direction is normalised without the vote.
+template <int kLaunch = 0, bool kProved = false>
 __device__ __forceinline__ Ray camera_ray(const LaunchParams &p, const FrameView &V, int x, int y, float jx,
                                           float jy) {
     // (a plain launch: at least 2 x 2 pixels and the host's short-division proof hold)
@@ -1897,7 +1959,8 @@ __device__ __forceinline__ Ray camera_ray(const LaunchParams &p, const FrameView
     }
     Ray ray;
     ray.start = mk(V.origin[0], V.origin[1], V.origin[2]);
-    ray.dir = normalize(sub(e3, s3));
+    if constexpr (kProved) ray.dir = normalize_proved<1>(sub(e3, s3), true);
+    else ray.dir = normalize(sub(e3, s3));
     return ray;
 }
 
@@ -1970,7 +2033,7 @@ __device__ __forceinline__ void render_wave_tile(const LaunchParams &p, Scene S,
     const uint32_t idx = static_cast<uint32_t>(local_row) * static_cast<uint32_t>(p.width) + static_cast<uint32_t>(x);
 
     if constexpr (!kAccum) {
-        const Ray ray = have_pre ? pre : camera_ray<kLaunch>(p, V, x, y, 0.0f, 0.0f);
+        const Ray ray = have_pre ? pre : camera_ray<kLaunch, kCameraProved(kDepth, kAccum, kShape, kLaunch)>(p, V, x, y, 0.0f, 0.0f);
 #if defined(RT_ABLATE_RAYGEN)
         (void)ray;
         const v3 col = mk(float(x), float(y), 0.0f);
@@ -1987,9 +2050,7 @@ __device__ __forceinline__ void render_wave_tile(const LaunchParams &p, Scene S,
         // general kernel, which reads the proof's answer from the launch. Never
         // the Monte-Carlo depth-0 kernels (no plain launch accumulates; their
         // own A/B was not made), the primary-hit kernel or a recursive one.
-        constexpr int kRoom = !kRoomFast ? kRoomGeneral
-                              : kPlain && (kShape & kShapeRoom) != 0 ? kRoomFastShape
-                              : kShape == 0 ? kRoomFastUniform : kRoomGeneral;
+        constexpr int kRoom = room_path(kDepth, kAccum, kShape, kLaunch);
         if constexpr (kRoom == kRoomFastUniform) S.room_fast = p.room_fast;
         const v3 col = trace0<kRoom>(S, ray, active);
 #endif
@@ -2154,6 +2215,22 @@ __device__ __forceinline__ void persistent_tile(const LaunchParams &p, float4 *l
     const Ray none{mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f)};
     render_wave_tile<0, false, kShape, kLaunch>(p, S, V, wx, wy, z, wave_pixel<kLaunch>(p, wx, wy), none, false);
 }
+// Timing probes (rt_internal.h kPadSalu, kPadValu; 0 by default): n more scalar
+// or vector adds per persistent tile, four independent chains on registers of
+// their own that live only here, so the frames stay the same.
+__device__ __forceinline__ void persistent_pad(int a, int b, int c, int d) {
+#pragma unroll
+    for (int k = 0; k < kPadSalu / 4; ++k)
+        asm volatile("s_add_u32 %0, %0, 1\n\ts_add_u32 %1, %1, 1\n\ts_add_u32 %2, %2, 1\n\ts_add_u32 %3, %3, 1"
+                     : "+s"(a), "+s"(b), "+s"(c), "+s"(d)
+                     :
+                     : "scc");
+    int va = a + static_cast<int>(threadIdx.x), vb = va + b, vc = va + c, vd = va + d;
+#pragma unroll
+    for (int k = 0; k < kPadValu / 4; ++k)
+        asm volatile("v_add_u32 %0, 1, %0\n\tv_add_u32 %1, 1, %1\n\tv_add_u32 %2, 1, %2\n\tv_add_u32 %3, 1, %3"
+                     : "+v"(va), "+v"(vb), "+v"(vc), "+v"(vd));
+}
 template <int kShape, int kLaunch>
 __device__ __forceinline__ void render_persistent0(float4 *lds) {
     static_assert((kLaunch & kLaunchPlain) != 0 && (kShape & kShapeMaskBytes) != 0, "plain shaped launches");
@@ -2209,6 +2286,7 @@ __device__ __forceinline__ void render_persistent0(float4 *lds) {
             if (z != held) persistent_refill(p, lds, z);
             held = z;
             RT_PHASE_COUNT(9, 1);  // tiles
+            persistent_pad(wx, wy, z, t);
             persistent_tile<kShape, kLaunch>(p, lds, z, wx, wy);
             if (++wx == (p.width + 7) / 8) {
                 wx = 0;
@@ -2308,7 +2386,8 @@ __global__ __launch_bounds__(kThreads) RT_OCCUPANCY void render_kernel(LaunchPar
     const Pixel own = wave_pixel<kLaunch>(p, own_wx, own_wy);
     RT_PHASE_AFTER(14, own.y);
     Ray own_ray{mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f)};
-    if (!queued && !kAccum) own_ray = camera_ray<kLaunch>(p, V, own.x, own.y, 0.0f, 0.0f);
+    if (!queued && !kAccum)
+        own_ray = camera_ray<kLaunch, kCameraProved(kDepth, kAccum, kShape, kLaunch)>(p, V, own.x, own.y, 0.0f, 0.0f);
     RT_PHASE_AFTER(15, own_ray.dir.x + own_ray.dir.y + own_ray.dir.z);
     RT_PHASE(10);
     if (tid < p.layout.blob_units) lds[tid] = first;

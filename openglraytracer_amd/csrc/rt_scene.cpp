@@ -614,6 +614,79 @@ bool camera_short_divisions(const float M[16], int width, int height) {
     return true;
 }
 
+// The view half of the norm proofs (rt_internal.h kNormProofs): for EVERY pixel
+// of a width x height frame the camera ray's d = e3 - s3 (camera_ray) has
+// finite components and |d|^2 inside inv_sqrt's [2^-96, 2^100], far inside.
+// It stands apart from camera_short_divisions (the general depth-0 kernels take
+// the room fast path with IEEE divisions too: either quotient is the correctly
+// rounded one). On that function's pixel box and corners, float64:
+//  * w is affine in (vx, vy): one sign at the eight corners and wmin, the
+//    smallest |w| there less the float32 evaluation's 2^-20 Tw, positive;
+//  * each point's components are ratios n_k / w of affine functions of
+//    (vx, vy) whose denominator keeps its sign, so they take their extremes
+//    over the box at the corners: |component| <= Cmax <= 2^40 keeps every
+//    |d_k| below 2^42, finite, and |d|^2 below 2^86;
+//  * with u the centre pixel's unit direction, u . e3 and u . s3 are such
+//    ratios too; G = min |u . e3 - u . s3| from their corner ranges is a lower
+//    bound of |d| for the exact points;
+//  * a float32 component differs from the exact one by at most eta =
+//    2^-20 (T + Cmax Tw) / wmin: at most eight roundings, 2^-21, of the sums
+//    of the terms' magnitudes T (numerators) and Tw (w), |w| >= wmin, the
+//    short division correctly rounded, and as much again for slack. The far
+//    point's w is a cancellation (Tw / wmin is 10^4 for the reference camera),
+//    which this carries. So the computed |d| >= G - 4 eta.
+// G >= 2^-40 and G >= 8 eta then leave |d|^2 >= 2^-82.
+bool camera_norm_range(const float M[16], int width, int height) {
+    const int hw = width / 2, hh = height / 2;
+    if (hw <= 0 || hh <= 0) return false;
+    const double vx[2] = {-1.0, static_cast<double>(width - hw) / hw};
+    const double vy[2] = {-1.0, static_cast<double>(height - hh) / hh};
+    const double ax = std::max(std::fabs(vx[0]), std::fabs(vx[1])), ay = std::max(std::fabs(vy[0]), std::fabs(vy[1]));
+    const auto point = [&](double x, double y, double z, double out[3]) {
+        const double w = double(M[3]) * x + double(M[7]) * y + double(M[11]) * z + double(M[15]);
+        for (int k = 0; k < 3; ++k)
+            out[k] = (double(M[k]) * x + double(M[4 + k]) * y + double(M[8 + k]) * z + double(M[12 + k])) / w;
+        return w;
+    };
+    double T = 0.0, Tw = 0.0, wmin = INFINITY, cmax = 0.0;
+    for (int k = 0; k < 4; ++k) {
+        const double t = std::fabs(M[k]) * ax + std::fabs(M[4 + k]) * ay + std::fabs(M[8 + k]) + std::fabs(M[12 + k]);
+        (k < 3 ? T : Tw) = std::max(k < 3 ? T : Tw, t);
+    }
+    double s[3], e[3], u[3];
+    point(0.0, 0.0, 0.5, s);
+    point(0.0, 0.0, 1.0, e);
+    double len = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        u[k] = e[k] - s[k];
+        len += u[k] * u[k];
+    }
+    len = std::sqrt(len);
+    if (!(len > 0.0 && std::isfinite(len))) return false;
+    for (double &x : u) x /= len;
+    double s_lo = INFINITY, s_hi = -INFINITY, e_lo = INFINITY, e_hi = -INFINITY, w_lo = INFINITY, w_hi = -INFINITY;
+    for (const double x : vx)
+        for (const double y : vy) {
+            const double ws = point(x, y, 0.5, s), we = point(x, y, 1.0, e);
+            for (const double w : {ws, we}) {
+                wmin = std::min(wmin, std::fabs(w));
+                w_lo = std::min(w_lo, w);
+                w_hi = std::max(w_hi, w);
+            }
+            for (int k = 0; k < 3; ++k) cmax = std::max(cmax, std::max(std::fabs(s[k]), std::fabs(e[k])));
+            const double ps = u[0] * s[0] + u[1] * s[1] + u[2] * s[2], pe = u[0] * e[0] + u[1] * e[1] + u[2] * e[2];
+            s_lo = std::min(s_lo, ps);
+            s_hi = std::max(s_hi, ps);
+            e_lo = std::min(e_lo, pe);
+            e_hi = std::max(e_hi, pe);
+        }
+    const double G = std::max(e_lo - s_hi, s_lo - e_hi);  // (the ranges apart, either way round)
+    wmin -= 0x1p-20 * Tw;
+    if (!(wmin > 0.0 && (w_lo > 0.0 || w_hi < 0.0))) return false;
+    const double eta = 0x1p-20 * (T + cmax * Tw) / wmin;
+    return cmax <= 0x1p40 && G >= 0x1p-40 && G >= 8.0 * eta;  // (a NaN fails)
+}
+
 // The kernel's frame_setup (rt_kernel.hip) for a one-view launch, on the
 // host: every work-group would otherwise derive the same constants (measured
 // 7 % of a 1080p depth-0 frame). Camera terms in float32 with the kernel's
@@ -1397,6 +1470,9 @@ int build_scene(const rt_object *objs, int n_objs, const rt_material *mats, int 
     for (int j = 0; j < n_lights && ds.room; ++j)
         if (lrec[j].dead == 0.0f && (j >= 32 || !((boxes[0].light_inside >> j) & 1u))) ds.room = 0;
     ds.room_fast = ds.room && room_record_identity(boxes[0]);
+    ds.norm = NormProof{};
+    if (ds.room_fast)
+        ds.norm = norm_proof_scene(boxes[0], sph.data(), smeta.data(), static_cast<int>(sph.size()), lrec.data(), n_lights);
     lay.n_mats = n_mats;
     lay.n_lights = n_lights;
     blob.assign(static_cast<size_t>(off > 0 ? off : 1), float4{0, 0, 0, 0});
@@ -1557,6 +1633,8 @@ int anim_plan(const char *who_c, const rt_object *base, const rt_object_anim *an
     // it alone), so build_scene's decision stands; a moving box never claims it.
     const bool static_room = L.n_boxes == 1 && !box_moves;
     if (!static_room) ds.room = ds.room_fast = 0;
+    // (norm_proof_scene read the spheres at their base places: no proof of a frame the device moves them in)
+    if (!static_room || n_moving > 0) ds.norm = NormProof{};
     // the kernel's static table
     AnimTable T{};
     T.n_boxes = static_room ? 0 : L.n_boxes;

@@ -12,7 +12,7 @@ Every build gets its own context and scene; each round times every build once
 launches on a non-default stream, about 60 ms of GPU work, so the clock is the
 sustained one the bench sees rather than a short burst's — rounds interleaved
 so clock drift hits all builds alike (AB_ROUNDS rounds, default 7). Prints the
-median and min per-frame (per-sample) kernel time and a hash of the frame.
+median, min and max per-frame (per-sample) kernel time and a hash of the frame.
 """
 import ctypes as C
 import hashlib
@@ -139,7 +139,7 @@ for cfg in cfgs:
             times[b].append(e0.elapsed_time(e1) / reps)
     for b in builds:
         t = np.array(times[b]) / max(batch, 1, mc_spp)  # per frame (per sample)
-        print("%-8s %-10s median %.5f ms  min %.5f ms  frame %s" % (cfg, b, np.median(t), t.min(), digests[b]),
-              flush=True)
+        print("%-8s %-10s median %.5f ms  min %.5f ms  max %.5f ms  frame %s" % (cfg, b, np.median(t), t.min(), t.max(),
+                                                                              digests[b]), flush=True)
     for b, (L, ctx) in libs.items():
         L.rt_scene_destroy(state[b])
