@@ -224,6 +224,26 @@ def norm_proof(objects, view, width, height, materials=None, lights=None):
     return tuple(flags), tuple(terms)
 
 
+def view_consts(objects, view, width, height, materials=None, lights=None):
+    """rt_debug_view_consts (host only): (culling flag, [(object index, x0, x1,
+    y0, y1) per sphere], [(object index, rx, ry, rz, inside) per box]) of the
+    host's frame constants for `view`; no records for a scene too large for them."""
+    mats = materials if materials is not None else reference_materials()
+    lights = lights if lights is not None else reference_lights()
+    oa, ma = (Object * max(len(objects), 1))(*objects), (Material * len(mats))(*mats)
+    la = (Light * max(len(lights), 1))(*lights)
+    n = 256  # rt_internal.h kMaxViewConsts
+    head, sph, ids, cam = (C.c_int32 * 3)(), (C.c_int32 * (5 * n))(), (C.c_int32 * (2 * n))(), (C.c_float * (3 * n))()
+    f = lib().rt_debug_view_consts
+    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    _check(f(oa, len(objects), ma, len(mats), la, len(lights), C.byref(view), width, height, head, sph, ids, cam))
+    spheres = [tuple(sph[5 * s:5 * s + 5]) for s in range(head[1])]
+    boxes = [(ids[2 * b], cam[3 * b], cam[3 * b + 1], cam[3 * b + 2], ids[2 * b + 1]) for b in range(head[2])]
+    return head[0], spheres, boxes
+
+
 def bench_objects(n_spheres, seed=0):
     o = (Object * (n_spheres + 1))()
     _check(lib().rt_bench_objects(n_spheres, seed, o))

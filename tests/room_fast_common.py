@@ -18,9 +18,9 @@ from oracle import scenes
 ROOM, FIXED, PLAIN, PERSISTENT = 16, 64, 1, 2  # rt_internal.h kShapeRoom, kShapeFixed, kLaunchPlain, kLaunchPersistent
 
 
-def room_proof(objs, view, w, h, lights=None):
+def room_proof(objs, view, w, h, lights=None, materials=None):
     """rt_debug_room_proof: (room, identity record, camera inside, short divisions, pinhole view)."""
-    mats = rt.reference_materials()
+    mats = materials if materials is not None else rt.reference_materials()
     lights = lights if lights is not None else rt.reference_lights()
     oa, ma, la = (rt.Object * len(objs))(*objs), (rt.Material * len(mats))(*mats), (rt.Light * len(lights))(*lights)
     out = (C.c_int32 * 5)()

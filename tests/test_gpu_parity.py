@@ -313,8 +313,8 @@ def test_batch_of_scenes_with_different_lights(gpu_ctx, n_views):
 def _inside_sphere_camera():
     cam = rt.Camera()
     cam.position[:] = (-3.0, 4.0, 1.2)  # inside config 1's red-glass sphere (centre (-3, 4, 1), r 2)
-    cam.angles[:] = (0.3, 1.1, 0.0)
-    cam.v_fov, cam.aspect, cam.near_plane, cam.far_plane = 1.5707964, 16.0 / 9.0, 0.1, 1000.0
+    cam.angles[:] = (17.0, 63.0, 0.0)  # degrees, like the field of view
+    cam.v_fov, cam.aspect, cam.near_plane, cam.far_plane = 90.0, 16.0 / 9.0, 0.1, 1000.0
     return cam
 
 
@@ -359,6 +359,10 @@ def test_host_frame_constants_equal_device_ones(gpu_ctx, case):
     if case in ("bench16", "shipped"):
         o = oracle_render(objs, w, h, depth, view_t)
         assert np.array_equal(single, o), parity_stats(single, o)
+    if case == "inside_sphere":
+        o = port.render(objs, w, h, depth, 0.0, camera=cam)
+        assert np.array_equal(single, o), parity_stats(single, o)
+        assert (port.render(objs, w, h, 0, 0.0, camera=cam, probe=2)[..., 0] == 0).all()  # (the sphere, all around)
 
 
 def test_async_stream_equals_sync(gpu_ctx):

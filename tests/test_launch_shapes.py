@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import openglraytracer_amd as rt
+from camera_common import oracle_view
 from conftest import parity_stats
 from openglraytracer_amd import abi
 from oracle import port, scenes
@@ -130,9 +131,11 @@ def test_other_launches_keep_their_run_time_tests(gpu_ctx, case, w, h):
         sc.close()
     assert on.tobytes() == off.tobytes()
     if case == "long_divisions":
-        # (no oracle frame of a scaled unprojection: its own option-off
-        # render, and a frame that shows the scene)
-        assert (on[..., :3] > 0).any()
+        # the oracle's frame of the scaled unprojection itself (and so, the
+        # quotients being the same, of the unscaled one)
+        o = oracle_view(objs, view, w, h, 0)
+        assert np.array_equal(on, o), parity_stats(on, o)
+        assert np.array_equal(o, port.render(objs, w, h, 0, 0.1)) and (on[..., :3] > 0).any()
         return
     o = port.render(objs, w, h, 0, 0.1, rows=rows)
     if case == "sharded":
