@@ -384,6 +384,57 @@ int rt_render_accumulate(rt_context *ctx, const rt_scene *scene, const rt_view *
                          int max_depth, int spp, int sample_offset, uint32_t seed, int jitter, int row_begin,
                          int row_end, float *accum_device, void *hip_stream);
 
+/* ---- adaptive anti-aliasing ----------------------------------------------
+ * Whitted's scheme: one sample per pixel, then supersampling only where the
+ * colour changes. The frame is rt_render's (width x height float4, row 0 =
+ * GL's bottom row), whole frames only: no row ranges, no shards.
+ *  1. The base frame B is rt_render_view of the whole frame at max_depth.
+ *  2. Pixel p is flagged iff some 4-neighbour q inside the frame — (x+-1, y),
+ *     (x, y+-1) — has max over c in {r, g, b} of |B[p][c] - B[q][c]| >
+ *     threshold. float32 throughout; the maximum is IEEE maxNum, so a channel
+ *     whose difference is NaN drops out and a NaN difference never flags; an
+ *     infinite one does (for a threshold below +inf). Both sides of an edge
+ *     are flagged; a 1 x 1 frame flags nothing; threshold +inf flags nothing
+ *     and a negative one every pixel that has a neighbour.
+ *  3. An unflagged pixel keeps B[p]. A flagged one becomes A[p] / (float)spp,
+ *     componentwise IEEE division (alpha stays 0), where A[p] is exactly what
+ *     rt_render_accumulate(spp, sample_offset 0, seed, jitter 1) leaves for
+ *     the pixel in a zeroed accumulator: the base sample is replaced, not
+ *     averaged in.
+ * `refined`, optional: one byte per pixel, 1 = flagged; device or host memory
+ * as `out` is. out_is_device and hip_stream are rt_render_view's (a non-NULL
+ * stream: asynchronous, device memory only). On the device: the base render
+ * (whatever kernel rt_render_view would pick), one edge kernel, one refine
+ * launch over the flagged pixels, all on the call's stream, nothing waited for
+ * or allocated in between after the first call at a size. The scratch
+ * (masks, live-tile list, counters) is the context's: a call on another stream
+ * waits on the device for the previous call's use of it.
+ * Errors: RT_ERR_INVALID for a NULL context ("null context ..."), scene, view
+ * or out, spp < 1, a NaN threshold, a bad size; RT_ERR_UNSUPPORTED when
+ * RT_OPT_OUTPUT is not RT_OUTPUT_RGBA32F, or for max_depth outside
+ * [0, RT_MAX_DEPTH]. RT_OPT_CULLING applies and leaves the output identical.
+ * With RT_OPT_TIMING, rt_last_kernel_ms covers the three launches; the
+ * rt_debug_last_* hooks keep reporting the base render. */
+int rt_render_aa_view(rt_context *ctx, const rt_scene *scene, const rt_view *view, int width, int height,
+                      int max_depth, int spp, uint32_t seed, float threshold, float *out, uint8_t *refined,
+                      int out_is_device, void *hip_stream);
+/* cam == NULL: the reference orbit camera at `time`. */
+int rt_render_aa(rt_context *ctx, const rt_scene *scene, const rt_camera *cam, float time, int width, int height,
+                 int max_depth, int spp, uint32_t seed, float threshold, float *out, uint8_t *refined,
+                 int out_is_device, void *hip_stream);
+/* Waits for the context's last anti-aliased render and returns its flagged
+ * pixels and its wave tiles (the kernels' 8 x 8 pixel units, aligned at
+ * multiples of 8) with a flagged pixel; either may be NULL. For tools and
+ * tests. RT_ERR_INVALID before the first such render. */
+int rt_aa_last_counts(rt_context *ctx, int64_t *pixels, int64_t *wave_tiles);
+/* The criterion itself on the host (no GPU, no context): step 2 over a frame
+ * in host memory. refined: one byte per pixel; tile_masks: one 64-bit word
+ * per wave tile, row-major ((width + 7) / 8 per row), bit l = pixel
+ * (8 wx + l % 8, 8 wy + l / 8), bits of pixels outside the frame 0. Either
+ * may be NULL, not both. The same text as the edge kernel evaluates. */
+int rt_aa_edge_mask(const float *rgba32f, int width, int height, float threshold, uint8_t *refined,
+                    uint64_t *tile_masks);
+
 /* ---- primary-hit buffers and pixel picking ------------------------------
  * What the kernel finds on the way to a pixel's colour, instead of the
  * colour: per pixel, the object its camera ray hits first
@@ -550,6 +601,12 @@ int rt_multi_last_ms(rt_multi *m, float *kernel_ms, float *gather_ms, float *ass
  * every launch with 0, runs the room kernels of the general launch shape.
  * Output is identical. */
 #define RT_OPT_ROOM_FAST 12
+/* RT_OPT_AA_QUEUED (default 1): how rt_render_aa*'s refine launch at depth 0
+ * and 1 finds its work. 1: a resident grid whose waves take the live wave
+ * tiles from the edge kernel's compact lists, as depths 2-9 always do. 0: one
+ * work-group per 16 x 16 pixel tile, which leaves at once when none of its
+ * pixels is flagged. Output is identical. */
+#define RT_OPT_AA_QUEUED 13
 /* (option 6, a tolerance tier that summed the recursion's colours forward
  * instead of mixing them on the way back up, measured even with the exact
  * walk and was removed: DESIGN.md §3.) */

@@ -94,6 +94,10 @@ def lib():
             "rt_render_hits": ([vp, vp, vp, f, i, i, i, i, i, vp, vp, vp, i, vp], i),
             "rt_render_hits_animated": ([vp, vp, vp, f, i, i, i, i, i, vp, vp, vp, i, vp], i),
             "rt_pick": ([vp, vp, vp, i, i, i, i, i, vp, vp, vp], i),
+            "rt_render_aa_view": ([vp, vp, vp, i, i, i, i, C.c_uint32, f, vp, vp, i, vp], i),
+            "rt_render_aa": ([vp, vp, vp, f, i, i, i, i, C.c_uint32, f, vp, vp, i, vp], i),
+            "rt_aa_last_counts": ([vp, vp, vp], i),
+            "rt_aa_edge_mask": ([vp, i, i, f, vp, vp], i),
         }
         for name, (args, res) in sig.items():
             fn = getattr(L, name)
@@ -390,6 +394,14 @@ class Context:
         the primary box hit without the matrix products (include/rt.h).
         Output identical either way."""
         _check(lib().rt_context_set(self._h, abi.RT_OPT_ROOM_FAST, 1 if on else 0))
+
+    def set_aa_queued(self, on):
+        """RT_OPT_AA_QUEUED: render_aa's refine launch at depth 0-1 takes the
+        live wave tiles from the edge kernel's lists on a resident grid (on,
+        the default, as depths 2-9 always do), or runs one work-group per
+        16 x 16 tile that leaves when none of its pixels is flagged. Output
+        identical either way."""
+        _check(lib().rt_context_set(self._h, abi.RT_OPT_AA_QUEUED, 1 if on else 0))
 
     def set_output(self, fmt):
         """RT_OPT_OUTPUT: abi.RT_OUTPUT_RGBA32F (float4 per pixel),
@@ -698,6 +710,64 @@ def render_accumulate(ctx, scene, accum_ptr, width, height, max_depth, spp, samp
     _check(lib().rt_render_accumulate(ctx.handle, scene.handle, C.byref(view), width, height, max_depth, spp,
                                       sample_offset, seed, 1 if jitter else 0, r0, r1, C.c_void_p(accum_ptr),
                                       C.c_void_p(stream) if stream else None))
+
+
+def render_aa(ctx, scene, width, height, max_depth, spp, threshold, seed=0, view=None, cam=None, time=0.0,
+              out=None, stream=None, want_mask=False):
+    """Adaptive anti-aliasing (rt_render_aa_view; with view None rt_render_aa
+    of `cam` — None: the orbit camera — at `time`): the base frame with every
+    pixel on a colour edge (a 4-neighbour differing by more than `threshold`
+    in some channel) replaced by the mean of `spp` jittered samples.
+    out None: host arrays, synchronously — the frame (height, width, 4)
+    float32, or (frame, mask) with want_mask, mask (height, width) uint8,
+    1 = supersampled. out a device pointer (e.g. tensor.data_ptr()): the frame
+    goes there, want_mask is then a device pointer for the byte plane (or
+    False), and with `stream` (a hipStream_t as int) the call is asynchronous."""
+    device = out is not None
+    if device:
+        frame, mask = None, None
+        out_ptr = C.c_void_p(out)
+        mask_ptr = C.c_void_p(want_mask) if want_mask else None
+    else:
+        frame = np.zeros((max(height, 1), max(width, 1), 4), np.float32)  # the C-ABI validates the size
+        mask = np.zeros((max(height, 1), max(width, 1)), np.uint8) if want_mask else None
+        out_ptr = C.c_void_p(frame.ctypes.data)
+        mask_ptr = C.c_void_p(mask.ctypes.data) if want_mask else None
+    tail = (width, height, max_depth, spp, seed, threshold, out_ptr, mask_ptr, 1 if device else 0,
+            C.c_void_p(stream) if stream else None)
+    if view is not None:
+        _check(lib().rt_render_aa_view(ctx.handle, scene.handle, C.byref(view), *tail))
+    else:
+        _check(lib().rt_render_aa(ctx.handle, scene.handle, C.byref(cam) if cam is not None else None, time, *tail))
+    if device:
+        return None
+    frame = frame[:height, :width]
+    return (frame, mask[:height, :width]) if want_mask else frame
+
+
+def aa_last_counts(ctx):
+    """(flagged pixels, wave tiles with a flagged pixel) of the context's last
+    render_aa, after waiting for it (rt_aa_last_counts)."""
+    px, tiles = C.c_int64(0), C.c_int64(0)
+    _check(lib().rt_aa_last_counts(ctx.handle, C.byref(px), C.byref(tiles)))
+    return px.value, tiles.value
+
+
+def aa_edge_mask(frame, threshold):
+    """The anti-aliasing criterion on the host (rt_aa_edge_mask; no GPU): for a
+    (height, width, 4) float32 frame, (mask, tile_masks) — mask (height, width)
+    uint8, 1 = a 4-neighbour differs by more than `threshold` in some channel;
+    tile_masks (ceil(height / 8), ceil(width / 8)) uint64, bit l of a word =
+    pixel (8 wx + l % 8, 8 wy + l / 8) of its 8 x 8 wave tile."""
+    frame = np.ascontiguousarray(frame, np.float32)
+    if frame.ndim != 3 or frame.shape[2] != 4:
+        raise ValueError("aa_edge_mask: a (height, width, 4) float32 frame")
+    height, width = frame.shape[:2]
+    mask = np.zeros((height, width), np.uint8)
+    tiles = np.zeros(((height + 7) // 8, (width + 7) // 8), np.uint64)
+    _check(lib().rt_aa_edge_mask(C.c_void_p(frame.ctypes.data), width, height, threshold,
+                                 C.c_void_p(mask.ctypes.data), C.c_void_p(tiles.ctypes.data)))
+    return mask, tiles
 
 
 def render_shard(ctx, scene, out_ptr, width, height, max_depth, block_rows, n_shards, shard,

@@ -28,6 +28,7 @@ RT_OPT_LAUNCH_SHAPES = 9
 RT_OPT_PERSISTENT0 = 10
 RT_OPT_FIXED_LAYOUT = 11
 RT_OPT_ROOM_FAST = 12
+RT_OPT_AA_QUEUED = 13
 RT_OUTPUT_RGBA32F = 0
 RT_OUTPUT_RGBA8 = 1
 RT_OUTPUT_RGB32F = 2

@@ -6,8 +6,13 @@
 //
 //   rt_cli [--width 1280] [--height 720] [--depth 0] [--time 0] [--frames 1]
 //          [--dt 0.016] [--scene shipped|spheres:N[:seed]|FILE.json] [--ppm out_%04d.ppm]
-//          [--pfm out_%04d.pfm] [--hits PREFIX] [--device 0] [--gpus N [--transport rccl|copy] [--block-rows 8]]
+//          [--pfm out_%04d.pfm] [--hits PREFIX] [--aa SPP[:THRESHOLD]] [--device 0]
+//          [--gpus N [--transport rccl|copy] [--block-rows 8]]
 //
+// --aa SPP[:THRESHOLD] renders every frame through rt_render_aa: pixels on a
+// colour edge (a 4-neighbour differing by more than THRESHOLD, 0.1 when
+// omitted, in some channel) become the mean of SPP jittered samples (seed 0).
+// One GPU only.
 // --hits PREFIX also writes every frame's primary-hit buffers (rt_render_hits)
 // as three PFMs: PREFIX.hit.pfm (object index, t, shadow mask, as floats),
 // PREFIX.normal.pfm and PREFIX.point.pfm (PREFIX may hold a %d for the frame
@@ -46,6 +51,8 @@ int main(int argc, char **argv) {
     int gpus = 1, block_rows = 8, transport = RT_MULTI_RCCL;
     float time0 = 0.0f, dt = 1.0f / 60.0f;
     std::string scene = "shipped", ppm, pfm, hits;
+    int aa_spp = 0;  // --aa: samples per flagged pixel; 0: one ray per pixel
+    float aa_threshold = 0.1f;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -62,6 +69,16 @@ int main(int argc, char **argv) {
         else if (a == "--ppm") ppm = next();
         else if (a == "--pfm") pfm = next();
         else if (a == "--hits") hits = next();
+        else if (a == "--aa") {  // SPP[:THRESHOLD]
+            const char *v = next();
+            char *end = nullptr;
+            aa_spp = static_cast<int>(std::strtol(v, &end, 10));
+            if (end && *end == ':') aa_threshold = std::strtof(end + 1, &end);
+            if (aa_spp < 1 || !end || *end != '\0' || end == v) {
+                std::fprintf(stderr, "rt_cli: --aa takes SPP[:THRESHOLD] with SPP >= 1\n");
+                return 2;
+            }
+        }
         else if (a == "--device") device = std::atoi(next());
         else if (a == "--gpus") gpus = std::atoi(next());
         else if (a == "--block-rows") block_rows = std::atoi(next());
@@ -69,12 +86,13 @@ int main(int argc, char **argv) {
         else {
             std::fprintf(stderr, "usage: rt_cli [--width W] [--height H] [--depth D] [--time T] [--frames K] "
                                  "[--dt S] [--scene shipped|spheres:N[:seed]|FILE.json] [--ppm PAT] [--pfm PAT] "
-                                 "[--hits PREFIX] [--device I] [--gpus N] [--transport rccl|copy] [--block-rows B]\n");
+                                 "[--hits PREFIX] [--aa SPP[:THRESHOLD]] [--device I] [--gpus N] [--transport rccl|copy] [--block-rows B]\n");
             return 2;
         }
     }
     if (gpus < 1) { std::fprintf(stderr, "rt_cli: --gpus must be >= 1\n"); return 2; }
     if (!hits.empty() && gpus > 1) { std::fprintf(stderr, "rt_cli: --hits renders on one GPU (not with --gpus above 1)\n"); return 2; }
+    if (aa_spp > 0 && gpus > 1) { std::fprintf(stderr, "rt_cli: --aa renders on one GPU (not with --gpus above 1)\n"); return 2; }
     std::vector<rt_context *> ctxs(gpus, nullptr);
     for (int g = 0; g < gpus; ++g)
         if (rt_create(device + g, &ctxs[g]) != RT_OK) return fail("rt_create");
@@ -141,11 +159,22 @@ int main(int argc, char **argv) {
             if (rt_render_multi(group, scs.data(), has_cam ? &cam : nullptr, t, width, height, depth, block_rows,
                                 frame.data(), 0) != RT_OK)
                 return fail("rt_render_multi");
+        } else if (aa_spp > 0) {
+            if (rt_render_aa(ctx, scs[0], has_cam ? &cam : nullptr, t, width, height, depth, aa_spp, 0u, aa_threshold,
+                             frame.data(), nullptr, 0, nullptr) != RT_OK)
+                return fail("rt_render_aa");
         } else if (rt_render(ctx, scs[0], has_cam ? &cam : nullptr, t, width, height, depth, 0, height, frame.data(),
                              0, nullptr) != RT_OK) {
             return fail("rt_render");
         }
         const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (aa_spp > 0) {
+            int64_t px = 0, tiles = 0;
+            if (rt_aa_last_counts(ctx, &px, &tiles) != RT_OK) return fail("rt_aa_last_counts");
+            std::printf("frame %d aa %d spp, threshold %g: %lld of %lld pixels supersampled, in %lld wave tiles\n", k,
+                        aa_spp, aa_threshold, static_cast<long long>(px), static_cast<long long>(width) * height,
+                        static_cast<long long>(tiles));
+        }
         if (group) {
             std::vector<float> kms(gpus, 0.0f);
             float gms = 0.0f, ams = 0.0f;

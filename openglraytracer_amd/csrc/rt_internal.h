@@ -748,6 +748,54 @@ static_assert(sizeof(HitTargets) == 32 && sizeof(LaunchParams) + sizeof(HitTarge
 // Launches hits_kernel (not a row of the render table: select_kernel and
 // find_kernel do not know it), tiled, on `stream`.
 hipError_t launch_hits(LaunchParams &p, const HitTargets &o, hipStream_t stream);
+// Adaptive anti-aliasing (rt_render_aa*; rt_aa.h has the criterion). A call's
+// scratch, per context: the wave tiles' 64-bit masks (aa_mask_slot's order),
+// the compact lists of the live tiles (wy * tiles_x + wx, in the order the
+// edge kernel's waves arrive) and their counters, zeroed on the call's stream.
+// One list with one counter took 25 ns per live tile (two atomics on one
+// line: 75 us of edge kernel for config 2's 2,974 live tiles at 1080p, 725 us
+// for config 3's 30,756 at 2160p), so there are kAaQueues lists, each with a
+// counter on a 256-B line of its own, as the render kernels' queues have
+// theirs. Work-group tile g (row-major) appends to list g % kAaQueues: the
+// lists are spatially interleaved and hold at most aa_queue_cap tiles each.
+constexpr int kAaQueues = 32;
+static_assert((kAaQueues & (kAaQueues - 1)) == 0 && kAaQueues <= 32, "masked with kAaQueues - 1; polled by one half-wave");
+struct AaQueue {
+    // one atomic per live tile adds (its flagged pixels << 32) | 1: the low
+    // word is the list's length (and the tile's place in it), the high word
+    // the flagged pixels of the list's tiles (a frame has at most 2^32 pixels)
+    unsigned long long count;
+    int32_t head;  // the refine launch's item counter
+    int32_t pad[61];
+};
+static_assert(sizeof(AaQueue) == 256, "a counter per 256-B line");
+// Tiles a list holds at most: four per work-group tile of its share.
+inline int aa_queue_cap(int width, int height) {
+    const long long groups = static_cast<long long>((width + 15) / 16) * ((height + 15) / 16);
+    return static_cast<int>((groups / kAaQueues + 1) * 4);
+}
+// The second kernel argument of the edge and refine kernels, as HitTargets is
+// the hits kernel's; LaunchParams is unchanged.
+struct AaTargets {
+    unsigned long long *masks;
+    int32_t *list;  // kAaQueues x queue_cap
+    AaQueue *queues;
+    uint8_t *refined;  // one byte per pixel, 1 = flagged; nullptr: not wanted
+    float threshold;
+    int32_t queue_cap;
+};
+static_assert(sizeof(AaTargets) == 40 && sizeof(LaunchParams) + sizeof(AaTargets) <= 6144, "kernel argument block");
+// The edge kernel over the frame at p.out (p.width x p.height float4), one
+// wave per wave tile: masks, list, counters and the refined plane.
+hipError_t launch_aa_edge(const LaunchParams &p, const AaTargets &a, hipStream_t stream);
+// The refine launch (not a row of the render table): the general Monte-Carlo
+// body over the flagged pixels, p.spp jittered samples from sample 0 with
+// p.seed, their mean stored over the base pixel at p.out. Tiled (depths 0-1
+// with queued01 false): a work-group per 16 x 16 tile that leaves when its
+// four masks are zero. Queued (depths 2-9 always): a resident grid (h.n_cu)
+// that takes the live tiles from the lists.
+hipError_t launch_aa_refine(LaunchParams &p, const AaTargets &a, const LaunchHost &h, int max_depth, bool queued01,
+                            hipStream_t stream);
 
 // rt_api.cpp
 void set_error(const std::string &msg);
@@ -802,6 +850,16 @@ struct rt_context {
     size_t staging_px = 0;
     float4 *hits_staging = nullptr;  // the same for rt_render_hits*: three planes of hits_staging_px records
     size_t hits_staging_px = 0;
+    int aa_queued = 1;  // RT_OPT_AA_QUEUED
+    // adaptive anti-aliasing (rt_render_aa*): one grow-only device allocation
+    // [queue counters][masks][lists][refined plane of a host-destination call],
+    // sized for aa_slots mask slots (whole work-group tiles) and aa_px pixels; the
+    // event follows the last call's use of it (and of `staging`), and the next
+    // call's stream waits for it on the device
+    void *aa_scratch = nullptr;
+    size_t aa_slots = 0, aa_px = 0;
+    hipEvent_t aa_done = nullptr;
+    bool aa_used = false;
     bool timed = false;
     int culling = 1;  // RT_OPT_CULLING
     int timing = 1;   // RT_OPT_TIMING

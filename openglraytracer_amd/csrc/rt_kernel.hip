@@ -39,6 +39,7 @@
 #include <cstring>
 #include <string>
 
+#include "rt_aa.h"
 #include "rt_internal.h"
 
 namespace rtamd {
@@ -2668,6 +2669,274 @@ void hits_kernel(LaunchParams p, HitTargets o) {
     hits_wave_tile(p, o, S, V, own_wx, own_wy, own, own_ray);
 }
 
+// ---- adaptive anti-aliasing (rt_render_aa*) ---------------------------------
+// Three launches on the call's stream: the base frame (a render like any
+// other, launch_render), the edge kernel over the frame just written, and the
+// refine launch, which supersamples the flagged pixels and stores each one's
+// mean over its base colour. Both new kernels take their extra arguments in a
+// second kernel argument (AaTargets), as the hits kernel does.
+//
+// The edge kernel: one wave per 8x8 wave tile in render_wave_tile's lane
+// mapping, four to a work-group as the render kernels have them. A lane loads
+// its own record; its 4-neighbours' come from the neighbouring lanes where
+// they lie in the tile (ds_bpermute) and from the frame where they lie past
+// the tile's edge: the lanes of the tile's outer columns load one horizontal
+// halo record, those of its outer rows one vertical one. The three loads are
+// issued together and nothing waits on a comparison (with a load per
+// neighbour behind the criterion's short circuit a wave made up to five round
+// trips in a row). Per pair, rt_aa.h's aa_pair_differs; the wave's ballot is
+// the tile's mask. Lane 0 writes it to the tile's slot — every slot of the
+// grid, the tiles past the frame's edge included, so a refine work-group
+// reads its four unconditionally — and, for a live tile, appends the tile to
+// its work-group's list with one atomic, which counts the list's tiles and
+// their flagged pixels at once (AaQueue::count).
+__device__ __forceinline__ float4 shuffle4(float4 v, int src) {
+    return make_float4(__shfl(v.x, src), __shfl(v.y, src), __shfl(v.z, src), 0.0f);
+}
+__global__ __launch_bounds__(kThreads) void aa_edge_kernel(const float4 *frame, int width, int height, AaTargets a) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int wx = static_cast<int>(blockIdx.x) * kWavesX + wave % kWavesX;
+    const int wy = static_cast<int>(blockIdx.y) * kWavesY + wave / kWavesX;
+    const int col = lane & 7, row = lane >> 3;
+    const int x = wx * 8 + col, y = wy * 8 + row;
+    const bool inside = x < width && y < height;
+    // the neighbours inside the frame
+    const bool has_l = inside && x > 0, has_r = inside && x + 1 < width;
+    const bool has_d = inside && y > 0, has_u = inside && y + 1 < height;
+    const size_t w = static_cast<size_t>(width);
+    const size_t at = static_cast<size_t>(y) * w + static_cast<size_t>(x);  // (read only where `inside`)
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 own = inside ? frame[at] : zero;
+    const bool halo_h = col == 0 ? has_l : (col == 7 && has_r), halo_v = row == 0 ? has_d : (row == 7 && has_u);
+    const float4 hh = halo_h ? frame[col == 0 ? at - 1 : at + 1] : zero;
+    const float4 vv = halo_v ? frame[row == 0 ? at - w : at + w] : zero;
+    const float4 sl = shuffle4(own, lane - 1), sr = shuffle4(own, lane + 1);
+    const float4 sd = shuffle4(own, lane - 8), su = shuffle4(own, lane + 8);
+    const float4 nl = col == 0 ? hh : sl, nr = col == 7 ? hh : sr, nd = row == 0 ? vv : sd, nu = row == 7 ? vv : su;
+    const float c[3] = {own.x, own.y, own.z};
+    const float l[3] = {nl.x, nl.y, nl.z}, r[3] = {nr.x, nr.y, nr.z}, d[3] = {nd.x, nd.y, nd.z}, u[3] = {nu.x, nu.y, nu.z};
+    // (all four pairs evaluated, then combined: no branch between them)
+    const bool dl = aa_pair_differs(c, l, a.threshold), dr = aa_pair_differs(c, r, a.threshold);
+    const bool dd = aa_pair_differs(c, d, a.threshold), du = aa_pair_differs(c, u, a.threshold);
+    const bool flagged = (has_l && dl) || (has_r && dr) || (has_d && dd) || (has_u && du);
+    const uint64_t mask = wave_ballot(flagged);
+    if (inside && a.refined) a.refined[at] = flagged ? 1 : 0;
+    if (lane == 0) {
+        a.masks[aa_mask_slot(width, wx, wy)] = mask;
+        if (mask != 0) {  // (a live tile lies inside the frame: its list holds a place for each such tile of its groups)
+            const unsigned group = blockIdx.y * gridDim.x + blockIdx.x;
+            const int q = static_cast<int>(group & (kAaQueues - 1));
+            const unsigned long long add = (static_cast<unsigned long long>(__builtin_popcountll(mask)) << 32) | 1ull;
+            const unsigned long long old = atomicAdd(&a.queues[q].count, add);
+            a.list[static_cast<size_t>(q) * a.queue_cap + static_cast<uint32_t>(old)] = wy * aa_tiles_x(width) + wx;
+        }
+    }
+}
+
+// One wave tile of the refine launch: render_wave_tile's Monte-Carlo branch of
+// the general kernels (kShape 0, a whole unsharded frame, one view), with the
+// lane's `active` the tile's mask bit, jitter on, samples [0, spp), and the
+// epilogue a store of the mean. 0.0f + acc is what rt_render_accumulate leaves
+// in a zeroed accumulator (a sum of -0 becomes +0), the division is IEEE, and
+// alpha stays 0 (0 / spp).
+template <int kDepth>
+__device__ __forceinline__ void refine_wave_tile(const LaunchParams &p, Scene S, const FrameView &V, int wx, int wy,
+                                                 uint64_t mask) {
+    S.cull = V.cull;
+    S.room = 0;
+    S.room_fast = 0;
+    S.cam_terms = 1;
+    if (!S.cull) S.cbplane = nullptr;  // (culling off: every box tested)
+    if (mask == 0) return;
+    const int lane = threadIdx.x & 63;
+    const bool active = ((mask >> lane) & 1u) != 0;  // (a flagged pixel lies inside the frame)
+    const int x = wx * 8 + (lane & 7), row = wy * 8 + (lane >> 3);
+    const int y = x < p.width && row < p.height ? row : wy * 8;  // (wave_pixel's row of a lane past the frame)
+    S.tx0 = wx * 8;
+    S.tx1 = S.tx0 + 7;
+    S.ty0 = wy * 8;
+    S.ty1 = S.ty0 + 7;
+    const uint32_t pixel = static_cast<uint32_t>(y) * static_cast<uint32_t>(p.width) + static_cast<uint32_t>(x);
+    v3 acc = mk(0.0f, 0.0f, 0.0f);
+    for (int smp = 0; smp < p.spp; ++smp) {
+        const uint32_t sid = static_cast<uint32_t>(smp);
+        const float jx = jitter_u(p.seed, sid, pixel, 0u), jy = jitter_u(p.seed, sid, pixel, 1u);
+        v3 col = mk(0.0f, 0.0f, 0.0f);
+        if constexpr (kDepth == 0) col = trace0(S, camera_ray(p, V, x, y, jx, jy), active);
+        else trace_tree<kDepth>(S, camera_ray(p, V, x, y, jx, jy), active, [&](v3 c) { col = c; });
+        acc = add(acc, col);
+    }
+    if (active) {
+        const float n = static_cast<float>(p.spp);
+        p.out[pixel] = make_float4((0.0f + acc.x) / n, (0.0f + acc.y) / n, (0.0f + acc.z) / n, 0.0f);
+    }
+}
+
+// The refine kernel of depth kDepth: hits_kernel's prologue (written out once
+// more, for the reason given there) behind the early exit, then the wave's
+// tiles.
+//  * Tiled (kQueued false; depths 0-1): a work-group per 16x16 tile, wave w its
+//    quadrant. The group's four masks lie side by side (aa_mask_slot): one
+//    scalar load, and a group without a flagged pixel leaves before it touches
+//    the scene.
+//  * Queued (every depth; the recursive ones always): a resident grid over the
+//    edge kernel's lists, their lengths read here. Wave g serves list
+//    g % kAaQueues: every item comes from the list's counter (AaQueue::head,
+//    zeroed on the stream), the first one while the scene is staged, the others
+//    when the wave has finished its tile. A wave whose list has run dry
+//    polls all lists' counters at once (one lane each, one round trip), moves
+//    to the next one with items left and leaves when there is none: the launch
+//    ends on wave-tile granularity whatever the lists' lengths. A work-group
+//    whose first wave's number is not below the live tiles' count leaves before
+//    the staging (work-group 0 never does while a tile is live, and any wave
+//    that stays can reach every list).
+struct AaGroupMasks {
+    uint32_t w[8];
+};
+// The kernel's second argument in the kernel-argument segment, behind LaunchParams.
+using AaArgs = const __attribute__((address_space(4))) AaTargets *;
+__device__ __forceinline__ AaArgs aa_args() {
+    static_assert(sizeof(LaunchParams) % alignof(AaTargets) == 0, "the second argument follows the first without padding");
+    AaArgs a = (AaArgs)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() +
+                        sizeof(LaunchParams));
+    asm volatile("" : "+s"(a));
+    return a;
+}
+// Asks for the next item of list q (lane 0; the answer is read with
+// readfirstlane where it is needed, so the round trip runs beside other work).
+__device__ __forceinline__ int aa_fetch(const AaTargets &a, int q, int lane) {
+    int v = 0;
+    if (lane == 0) v = atomicAdd(&a.queues[q].head, 1);
+    return v;
+}
+// Occupancy: the Monte-Carlo siblings' targets, but 5 waves per SIMD for the
+// queued depth-0 kernel. At the sibling's 6 (80 VGPRs) the item loop's state
+// took it to 40 B of scratch per lane against the sibling's 36; a refine
+// launch rarely fills the chip anyway (config 2 at 1080p: 2,974 live tiles
+// for 1,024 SIMDs).
+constexpr int kWpe0Aa = 5;
+template <int kDepth, bool kQueued>
+__global__ __launch_bounds__(kThreads)
+    __attribute__((amdgpu_waves_per_eu(kDepth == 0 ? (kQueued ? kWpe0Aa : RT_WPE0_MC) : RT_WAVES_PER_EU(kDepth, 0))))
+void aa_refine_kernel(LaunchParams p, AaTargets a) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds[];
+    static_assert(kQueued || !kQueuedDepth(kDepth), "the recursive depths take their tiles from the lists");
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    using CMasks = const __attribute__((address_space(4))) AaGroupMasks *;
+    using CInts = const __attribute__((address_space(4))) int32_t *;
+    using CWords = const __attribute__((address_space(4))) uint32_t *;
+    uint64_t own_mask = 0;
+    int q = 0, pending = 0;
+    if constexpr (kQueued) {
+        int total = 0;  // (the edge kernel wrote the counts: a launch before this one)
+#pragma unroll
+        for (int k = 0; k < kAaQueues; ++k) total += static_cast<int>(*(CWords)(&a.queues[k].count));
+        if (static_cast<int>(blockIdx.x) * (kThreads / 64) >= total) return;
+        q = (static_cast<int>(blockIdx.x) * (kThreads / 64) + wave) & (kAaQueues - 1);
+        pending = aa_fetch(a, q, threadIdx.x & 63);  // (answered while the scene is staged)
+    } else {
+        const size_t group = static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x;
+        const AaGroupMasks m = cload((CMasks)(a.masks) + group);
+        if ((m.w[0] | m.w[1] | m.w[2] | m.w[3] | m.w[4] | m.w[5] | m.w[6] | m.w[7]) == 0u) return;
+        const uint32_t lo = wave == 0 ? m.w[0] : (wave == 1 ? m.w[2] : (wave == 2 ? m.w[4] : m.w[6]));
+        const uint32_t hi = wave == 0 ? m.w[1] : (wave == 1 ? m.w[3] : (wave == 2 ? m.w[5] : m.w[7]));
+        own_mask = static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32);
+    }
+    __builtin_amdgcn_s_setprio(1);
+    const FrameView &V = p.view[0];
+    const float4 *blob = static_cast<const float4 *>(p.scene);
+    const int tid = threadIdx.x;
+    float4 first = make_float4(0.0f, 0.0f, 0.0f, 0.0f), fc = first;
+    if (tid < p.layout.blob_units) first = blob[tid];
+    if (tid < p.n_frame_consts) fc = p.frame_consts[tid];
+    float4 *const views = lds + p.layout.blob_units;
+    float4 *sph_cam = views;
+    int4 *sph_px = reinterpret_cast<int4 *>(views + p.layout.n_spheres);
+    float4 *box_cam = reinterpret_cast<float4 *>(sph_px + p.layout.n_spheres);
+    if (tid < p.layout.blob_units) lds[tid] = first;
+    for (int i = tid + kThreads; i < p.layout.blob_units; i += kThreads) lds[i] = blob[i];
+    if (p.n_frame_consts > 0) {
+        if (tid < p.n_frame_consts) views[tid] = fc;
+    } else {
+        frame_setup(p, V, sph_cam, sph_px, box_cam);
+    }
+    __syncthreads();
+    __builtin_amdgcn_s_setprio(0);
+    const SceneLayout &L = p.layout;
+    Scene S;
+    S.sph = lds + L.off_spheres;
+    S.smeta = reinterpret_cast<const int4 *>(lds + L.off_smeta);
+    S.sph_cam = sph_cam;
+    S.sph_px = sph_px;
+    S.box = reinterpret_cast<const BoxRec *>(lds + L.off_boxes);
+    S.box_cam = box_cam;
+    S.mat = reinterpret_cast<const MatRec *>(lds + L.off_mats);
+    S.light = reinterpret_cast<const LightRec *>(lds + L.off_lights);
+    S.lm = reinterpret_cast<const LightMatRec *>(lds + L.off_lightmat);
+    S.bvh = lds + L.off_bvh;
+    S.blink = reinterpret_cast<const uint32_t *>(lds + L.off_blink);
+    S.cone = L.off_cone >= 0 ? reinterpret_cast<const ShadowCone *>(lds + L.off_cone) : nullptr;
+    S.dmask = L.off_dmask >= 0 ? reinterpret_cast<const char *>(lds + L.off_dmask) : nullptr;
+    S.dmask_n = L.dmask_n;
+    S.dmask_bytes = L.dmask_bytes;
+    S.dmask_box = L.dmask_box;
+    S.cbplane = L.off_bplane >= 0 ? (const __attribute__((address_space(4))) float4 *)(blob + L.off_bplane) : nullptr;
+    // (as render_kernel: the wide masks and the lists at the recursive depths only)
+    S.gmask = kDepth >= 2 && L.off_gmask >= 0 ? reinterpret_cast<const uint64_t *>(blob + L.off_gmask) : nullptr;
+    S.gwords = L.gmask_words;
+    S.glist = S.gmask && L.off_glist >= 0 ? reinterpret_cast<const uint4 *>(blob + L.off_glist) : nullptr;
+    S.olist = kDepth >= 2 && L.off_olist >= 0 ? reinterpret_cast<const uint4 *>(blob + L.off_olist) : nullptr;
+    S.cbox = (const __attribute__((address_space(4))) BoxRec *)(blob + L.off_boxes);
+    S.clight = (const __attribute__((address_space(4))) LightRec *)(blob + L.off_lights);
+#ifdef RT_UNIFORM_MAT
+    S.cmat = (const __attribute__((address_space(4))) MatRec *)(blob + L.off_mats);
+    S.clm = (const __attribute__((address_space(4))) LightMatRec *)(blob + L.off_lightmat);
+#endif
+    S.nbvh = L.n_bvh;
+    S.ns = L.n_spheres;
+    S.nb = L.n_boxes;
+    S.nl = L.n_lights;
+    S.nm = L.n_mats;
+    if constexpr (!kQueued) {
+        refine_wave_tile<kDepth>(p, S, V, static_cast<int>(blockIdx.x) * kWavesX + wave % kWavesX,
+                                 static_cast<int>(blockIdx.y) * kWavesY + wave / kWavesX, own_mask);
+    } else {
+        static_assert(kAaQueues == 32, "the poll below: a bit per list in one 32-bit word");
+        const int lane = threadIdx.x & 63;
+        const int wtx = aa_tiles_x(p.width);
+        int cur = __builtin_amdgcn_readfirstlane(pending);
+        for (;;) {
+            // The second argument read again per item, through a pointer the compiler cannot see
+            // through (render_persistent0's way with LaunchParams): held in scalar registers
+            // across the tile, its ten words put the depth-0 kernel above its sibling's scratch.
+            const AaTargets ka = cload(aa_args());
+            if (cur >= static_cast<int>(*(CWords)(&ka.queues[q].count))) {
+                // the list is dry: which lists have items left (the counters as they are now)
+                bool more = false;
+                if (lane < kAaQueues)
+                    more = __hip_atomic_load(&ka.queues[lane].head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <
+                           static_cast<int>(static_cast<uint32_t>(ka.queues[lane].count));
+                const uint32_t live = static_cast<uint32_t>(wave_ballot(more));
+                if (live == 0u) break;
+                const int from = (q + 1) & (kAaQueues - 1);  // the next one in turn
+                const uint64_t twice = static_cast<uint64_t>(live) | (static_cast<uint64_t>(live) << 32);
+                q = (from + __builtin_ctz(static_cast<uint32_t>(twice >> from))) & (kAaQueues - 1);
+                cur = __builtin_amdgcn_readfirstlane(aa_fetch(ka, q, lane));
+                continue;
+            }
+            const int tile = ((CInts)(ka.list))[static_cast<size_t>(q) * ka.queue_cap + cur];
+            const int wy = tile / wtx, wx = tile - wy * wtx;
+            CWords mw = (CWords)(ka.masks) + 2 * aa_mask_slot(p.width, wx, wy);
+            const uint64_t mask = static_cast<uint64_t>(mw[0]) | (static_cast<uint64_t>(mw[1]) << 32);
+            refine_wave_tile<kDepth>(p, S, V, wx, wy, mask);
+            // (not fetched ahead: a vector register held across the tile put the depth-0
+            // kernel 8 B of scratch above its Monte-Carlo sibling, for a round trip of
+            // about 2 us beside a tile of spp samples)
+            cur = __builtin_amdgcn_readfirstlane(aa_fetch(cload(aa_args()), q, lane));
+        }
+    }
+}
+
 // Resident work-groups per CU of a kernel at a dynamic LDS size (cached: the
 // occupancy query is host work).
 int groups_per_cu(const void *fn, size_t lds) {
@@ -2796,6 +3065,53 @@ hipError_t launch_hits(LaunchParams &p, const HitTargets &o, hipStream_t stream)
     const hipError_t e = hipLaunchKernel(reinterpret_cast<const void *>(&hits_kernel), grid, dim3(kThreads), args,
                                          lds_bytes(p.layout), stream);
     (void)hipGetLastError();  // (e is the launch's own status; no sticky error for a later check)
+    return e;
+}
+
+namespace {
+using AaRefineFn = void (*)(LaunchParams, AaTargets);
+// the queued kernel of every depth, and the tiled ones of depths 0-1
+constexpr AaRefineFn kAaRefine[RT_MAX_DEPTH + 1] = {
+    &aa_refine_kernel<0, true>, &aa_refine_kernel<1, true>, &aa_refine_kernel<2, true>, &aa_refine_kernel<3, true>,
+    &aa_refine_kernel<4, true>, &aa_refine_kernel<5, true>, &aa_refine_kernel<6, true>, &aa_refine_kernel<7, true>,
+    &aa_refine_kernel<8, true>, &aa_refine_kernel<9, true>};
+constexpr AaRefineFn kAaRefineTiled[2] = {&aa_refine_kernel<0, false>, &aa_refine_kernel<1, false>};
+}  // namespace
+
+hipError_t launch_aa_edge(const LaunchParams &p, const AaTargets &a, hipStream_t stream) {
+    const float4 *frame = p.out;
+    int width = p.width, height = p.height;
+    AaTargets targets = a;
+    void *args[] = {&frame, &width, &height, &targets};
+    const dim3 grid(aa_groups_x(width), aa_groups_y(height), 1);
+    const hipError_t e =
+        hipLaunchKernel(reinterpret_cast<const void *>(&aa_edge_kernel), grid, dim3(kThreads), args, 0, stream);
+    (void)hipGetLastError();  // (e is the launch's own status; no sticky error for a later check)
+    return e;
+}
+
+hipError_t launch_aa_refine(LaunchParams &p, const AaTargets &a, const LaunchHost &h, int max_depth, bool queued01,
+                            hipStream_t stream) {
+    if (max_depth < 0 || max_depth > RT_MAX_DEPTH) return hipErrorInvalidValue;
+    // one slice, the whole frame; a queued launch counts on the call's own counters
+    p.slice_begin = 0;
+    p.slice_rows = p.n_rows;
+    p.sched = nullptr;
+    const bool queued = kQueuedDepth(max_depth) || queued01;
+    const void *fn = reinterpret_cast<const void *>(queued ? kAaRefine[max_depth] : kAaRefineTiled[max_depth]);
+    const size_t lds = lds_bytes(p.layout);
+    dim3 grid(aa_groups_x(p.width), aa_groups_y(p.height), 1);
+    if (queued) {
+        // no more work-groups than are resident at once, nor than the frame's
+        // wave tiles could occupy (four each)
+        const long long groups = (static_cast<long long>(aa_tiles_x(p.width)) * aa_tiles_y(p.height) + 3) / 4;
+        const long long resident = h.n_cu > 0 ? static_cast<long long>(groups_per_cu(fn, lds)) * h.n_cu : groups;
+        grid = dim3(static_cast<unsigned>(groups < resident ? groups : resident), 1, 1);
+    }
+    AaTargets targets = a;
+    void *args[] = {&p, &targets};
+    const hipError_t e = hipLaunchKernel(fn, grid, dim3(kThreads), args, lds, stream);
+    (void)hipGetLastError();
     return e;
 }
 
@@ -2961,6 +3277,12 @@ hipError_t allow_large_lds(size_t bytes) {
         (void)hipFuncSetAttribute(row.fn(), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hits_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               static_cast<int>(bytes));
+    for (const AaRefineFn fn : kAaRefine)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  static_cast<int>(bytes));
+    for (const AaRefineFn fn : kAaRefineTiled)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  static_cast<int>(bytes));
     (void)hipGetLastError();  // do not leak a sticky error into the next launch check
     return hipSuccess;
 }

@@ -23,6 +23,8 @@
 #   acc          tools/ab_accuracy.py $ACC_ARGS
 #   probe        tools/probes/issue_probe (scalar issue rate)
 #   list         rocprofv3 -L (the box's counters)
+#   aa           tools/aa_time.py (adaptive anti-aliasing: timings, then a kernel trace run of its own), to aa_time.log
+#   bench25      one bench line each of config 2 and config 5
 # (Round 5 ran 29 one-off scripts of exactly these steps; git history keeps them.)
 set -uo pipefail
 tag=${1:?tag}; shift
@@ -60,4 +62,13 @@ if want stats; then step stats 300 python tools/stats.py stats ${CYC_ARGS:-confi
 if want phase; then step phase 300 env PHASE_DUMP=gpurun_out/$tag/phase.npz python tools/phase_trace.py config2 phase; fi
 if want acc; then step accuracy 600 python tools/ab_accuracy.py ${ACC_ARGS:-main}; fi
 if want probe; then step issue_probe 120 tools/probes/issue_probe 2.4; fi
+if want aa; then  # adaptive anti-aliasing: the timing run, a kernel trace run of its own, then the trace's rows
+  step aa_time 600 python tools/aa_time.py --out $out/aa_time.log
+  step aa_trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/aa_trace -o trace -- python tools/aa_time.py --child
+  step aa_kernels 60 python tools/aa_time.py --trace $out/aa_trace --append $out/aa_time.log
+fi
+if want bench25; then  # one bench line each of config 2 and config 5
+  step bench_config2 300 python bench.py --gpus 1 --steps 50 --warmup 5 --no-cpu-baseline
+  step bench_config5 300 python bench.py --gpus 1 --workload config5 --steps 3 --warmup 1 --no-cpu-baseline
+fi
 echo done

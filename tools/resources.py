@@ -63,6 +63,11 @@ def kernel_name(mangled):
         return "animate_kernel<%s>" % ("true" if m.group(1) == "1" else "false")
     if re.search(r"\d+hits_kernelE", mangled):  # the primary-hit kernel (rt_kernel.hip; not a row of the render table)
         return "hits_kernel"
+    m = re.search(r"\d+aa_refine_kernelILi(\d)ELb([01])EE", mangled)  # adaptive anti-aliasing (not rows either)
+    if m:  # depth, queued
+        return "aa_refine_kernel<%s,%s>" % (m.group(1), "true" if m.group(2) == "1" else "false")
+    if re.search(r"\d+aa_edge_kernelE", mangled):
+        return "aa_edge_kernel"
     return mangled
 
 
@@ -103,7 +108,7 @@ def resources(so):
     for r in out.values():
         if "vgpr" in r:
             r["waves_per_simd"] = min(8, 512 // max(8, -(-r["vgpr"] // 8) * 8))
-    return {k: v for k, v in out.items() if k.startswith(("render_kernel", "animate_kernel", "hits_kernel"))}
+    return {k: v for k, v in out.items() if k.startswith(("render_kernel", "animate_kernel", "hits_kernel", "aa_"))}
 
 
 def texts(so):
@@ -119,7 +124,7 @@ def texts(so):
                 m = re.match(r"^(?:[0-9a-f]+ )?<([^>]+)>:$", line)
                 if m:
                     cur = out.setdefault(m.group(1), [])
-                elif cur is not None and line.strip():
+                elif cur is not None and line.strip() and line.strip() != "...":  # (not the padding behind a function)
                     cur.append(re.sub(r"\s*//.*$", "", line).strip())  # (the address and encoding comment)
     return out
 
