@@ -488,6 +488,58 @@ int rt_render_hits_animated(rt_context *ctx, rt_anim *anim, const rt_camera *cam
 int rt_pick(rt_context *ctx, const rt_scene *scene, const rt_view *view, int width, int height, int x, int y,
             int flags, rt_hit *hit, float normal[3], float point[3]);
 
+/* ---- ray queries: caller-supplied rays -----------------------------------
+ * The same machinery behind a buffer of rays of any origin and direction
+ * instead of a pinhole view: a fisheye, orthographic, panoramic or thin-lens
+ * camera, a light probe, line-of-sight and range queries, rays continued from
+ * a hit that rt_render_hits reported.
+ *
+ * Ray i is traced as recursive_raytrace (raytrace_compute.glsl:1071-1105)
+ * traces a ray with that start and direction, at max_depth 0..RT_MAX_DEPTH.
+ * The direction is used as given, not normalised: the reference's rays are
+ * unit vectors, and t, the 10000 horizon and the shading assume that.
+ * Planes, each optional (NULL; not all four), one 16-byte record per ray:
+ * colors[i] = (r, g, b, 0) as rt_render writes a pixel; hits[i], normals[i],
+ * points[i] = rt_render_hits' records of the ray's first hit, a miss
+ * (-1, 0, 0, -1) and zeros. flags: RT_HITS_SHADOW as for rt_render_hits, dead
+ * lights included. max_depth applies to colors only. n_rays = 0 returns RT_OK
+ * and does nothing.
+ * buffers_are_device covers `rays` and every plane; host buffers go through
+ * one grow-only device buffer of the context. hip_stream as in rt_render (a
+ * non-NULL stream: asynchronous, device buffers only). At most two launches
+ * (colours, hits) on the call's stream. RT_OPT_CULLING applies and leaves the
+ * output identical; RT_OPT_OUTPUT does not apply; rt_last_kernel_ms covers the
+ * call's launches; the rt_debug_last_* hooks keep reporting the last render.
+ * Exact (bit for bit the reference's arithmetic) for every ray whose origin
+ * and direction are finite, wherever the origin lies and whatever the
+ * direction's length: a wave of 64 consecutive rays that holds an origin more
+ * than 1024 units from the world's origin on an axis, or a direction whose
+ * squared length differs from 1 by more than 2^-19, is traced without culling
+ * (slower, identical). A ray with a non-finite component gives an unspecified
+ * record for that ray alone.
+ * Errors: RT_ERR_INVALID for a NULL context ("null context ..."), a NULL
+ * scene, NULL rays with n_rays > 0, all four planes NULL, n_rays < 0 or
+ * > RT_MAX_RAYS, unknown flag bits, a stream with host buffers;
+ * RT_ERR_UNSUPPORTED for max_depth outside [0, RT_MAX_DEPTH] when colors is
+ * given. */
+typedef struct rt_ray {      /* 32 bytes: two 16-byte device loads per lane */
+    float origin[3]; float reserved0;   /* reserved*: ignored on input, any value */
+    float dir[3];    float reserved1;
+} rt_ray;
+#define RT_MAX_RAYS (1 << 28)
+int rt_trace_rays(rt_context *ctx, const rt_scene *scene, const rt_ray *rays, int64_t n_rays, int max_depth,
+                  int flags, float *colors, rt_hit *hits, float *normals, float *points, int buffers_are_device,
+                  void *hip_stream);
+/* The camera rays of a view in rt_render's pixel order: pixel (x, y) of rows
+ * [row_begin, row_end) at (y - row_begin) * width + x, origin = view->origin,
+ * direction = exactly what the render kernels compute for the pixel (the same
+ * text), reserved words 0. rt_trace_rays of them equals rt_render_view /
+ * rt_render_hits_view of the view byte for byte; perturb them for a custom
+ * camera. Errors as rt_render_view's (NULL pointer, bad size or row range, a
+ * stream with a host buffer: RT_ERR_INVALID). */
+int rt_view_rays(rt_context *ctx, const rt_view *view, int width, int height, int row_begin, int row_end,
+                 rt_ray *rays, int rays_are_device, void *hip_stream);
+
 /* ---- one frame on several GPUs of this process ----
  * The reference renders a frame with one glDispatchCompute(W, H, 1) +
  * glFinish (OpenGLRaytracer/main.cpp:228-238). A multi-GPU group deals the

@@ -98,6 +98,8 @@ def lib():
             "rt_render_aa": ([vp, vp, vp, f, i, i, i, i, C.c_uint32, f, vp, vp, i, vp], i),
             "rt_aa_last_counts": ([vp, vp, vp], i),
             "rt_aa_edge_mask": ([vp, i, i, f, vp, vp], i),
+            "rt_trace_rays": ([vp, vp, vp, C.c_int64, i, i, vp, vp, vp, vp, i, vp], i),
+            "rt_view_rays": ([vp, vp, i, i, i, i, vp, i, vp], i),
         }
         for name, (args, res) in sig.items():
             fn = getattr(L, name)
@@ -665,6 +667,74 @@ def pick(ctx, scene, width, height, x, y, view=None, time=0.0, shadow=True):
                          abi.RT_HITS_SHADOW if shadow else 0, C.byref(hit), C.c_void_p(normal.ctypes.data),
                          C.c_void_p(point.ctypes.data)))
     return hit, normal, point
+
+
+# ---- ray queries (rt_trace_rays, rt_view_rays) ------------------------------
+RAY_PLANES = ("colors", "hits", "normals", "points")
+
+
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def trace_rays(ctx, scene, rays, max_depth=0, colors=True, hits=False, normals=False, points=False, shadow=True,
+               stream=None):
+    """rt_trace_rays: traces caller-supplied rays and returns the requested
+    planes as a tuple, in RAY_PLANES' order.
+
+    rays: a numpy array of abi.RAY_DTYPE, or of float32 with 8 values per ray
+    (origin, reserved, direction, reserved), any shape; or a torch tensor on
+    the context's GPU, float32, contiguous, 8 values per ray. Directions are
+    used as given (not normalised). numpy in, numpy out, synchronously: colors
+    (n, 4) float32, hits (n,) abi.HIT_DTYPE, normals and points (n, 4) float32.
+    torch in, torch out on the same device: hits as (n, 4) int32 (the record's
+    four words; .cpu().numpy().view(abi.HIT_DTYPE) names them); with `stream`
+    (a hipStream_t as int) the call is asynchronous on that stream.
+    shadow=False: no shadow rays, hits' shadow = 0."""
+    want = dict(zip(RAY_PLANES, (colors, hits, normals, points)))
+    flags = abi.RT_HITS_SHADOW if shadow else 0
+    sp = C.c_void_p(stream) if stream else None
+    if _is_torch(rays):
+        import torch
+        if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8:
+            raise ValueError("rays: a contiguous float32 tensor on the GPU, 8 values per ray")
+        n = rays.numel() // 8
+        out = {k: torch.empty((max(n, 1), 4), dtype=torch.int32 if k == "hits" else torch.float32, device=rays.device)
+               for k in RAY_PLANES if want[k]}
+        ptrs = [C.c_void_p(out[k].data_ptr()) if k in out else None for k in RAY_PLANES]
+        _check(lib().rt_trace_rays(ctx.handle, scene.handle, C.c_void_p(rays.data_ptr()), n, max_depth, flags, *ptrs,
+                                   1, sp))
+        return tuple(out[k][:n] for k in RAY_PLANES if want[k])
+    a = np.ascontiguousarray(rays)
+    if a.dtype != abi.RAY_DTYPE:
+        a = np.ascontiguousarray(a, np.float32)
+        if a.size % 8:
+            raise ValueError("rays: abi.RAY_DTYPE records, or 8 float32 values per ray")
+        a = a.reshape(-1, 8)
+    n = a.size if a.dtype == abi.RAY_DTYPE else a.shape[0]
+    out = {k: (np.zeros(max(n, 1), abi.HIT_DTYPE) if k == "hits" else np.zeros((max(n, 1), 4), np.float32))
+           for k in RAY_PLANES if want[k]}
+    ptrs = [C.c_void_p(out[k].ctypes.data) if k in out else None for k in RAY_PLANES]
+    _check(lib().rt_trace_rays(ctx.handle, scene.handle, C.c_void_p(a.ctypes.data), n, max_depth, flags, *ptrs, 0, sp))
+    return tuple(out[k][:n] for k in RAY_PLANES if want[k])
+
+
+def view_rays(ctx, view, width, height, rows=None, device=False):
+    """rt_view_rays: the camera rays of `view` for rows [r0, r1) in rt_render's
+    pixel order — a numpy array (r1-r0, width) of abi.RAY_DTYPE, or with
+    device=True a float32 torch tensor (r1-r0, width, 8) on the context's GPU.
+    trace_rays of them equals render / render_hits of the view."""
+    r0, r1 = rows if rows is not None else (0, height)
+    shape = (max(r1 - r0, 1), max(width, 1))  # the C-ABI validates the range
+    if device:
+        import torch
+        out = torch.empty(shape + (8,), dtype=torch.float32, device="cuda:%d" % ctx.device)
+        _check(lib().rt_view_rays(ctx.handle, C.byref(view), width, height, r0, r1, C.c_void_p(out.data_ptr()), 1,
+                                  None))
+        return out[: r1 - r0, :width]
+    out = np.zeros(shape, abi.RAY_DTYPE)
+    _check(lib().rt_view_rays(ctx.handle, C.byref(view), width, height, r0, r1, C.c_void_p(out.ctypes.data), 0, None))
+    return out[: r1 - r0, :width]
 
 
 def render_batch(ctx, scene, out_ptr, width, height, max_depth, views, block_rows=8, n_shards=1,

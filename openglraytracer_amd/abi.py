@@ -93,6 +93,21 @@ HIT_DTYPE = np.dtype([("object", np.int32), ("t", np.float32), ("shadow", np.uin
 assert HIT_DTYPE.itemsize == C.sizeof(Hit) == 16
 
 
+RT_MAX_RAYS = 1 << 28
+
+
+class Ray(C.Structure):
+    """rt_ray: one caller-supplied ray (rt_trace_rays, rt_view_rays), 32 bytes;
+    the reserved words are ignored on input."""
+    _fields_ = [("origin", F3), ("reserved0", C.c_float), ("dir", F3), ("reserved1", C.c_float)]
+
+
+# the same record as a numpy dtype (the `rays` buffer of trace_rays)
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("reserved0", np.float32), ("dir", np.float32, 3),
+                      ("reserved1", np.float32)])
+assert RAY_DTYPE.itemsize == C.sizeof(Ray) == 32
+
+
 def array(struct, items):
     """Build a ctypes array of `struct` from a list of structs."""
     arr = (struct * max(len(items), 1))()

@@ -796,6 +796,49 @@ hipError_t launch_aa_edge(const LaunchParams &p, const AaTargets &a, hipStream_t
 // that takes the live tiles from the lists.
 hipError_t launch_aa_refine(LaunchParams &p, const AaTargets &a, const LaunchHost &h, int max_depth, bool queued01,
                             hipStream_t stream);
+// Ray queries (rt_trace_rays, rt_view_rays): the second kernel argument of the
+// ray kernels, as HitTargets is the hits kernel's. `rays`: two 16-B records per
+// ray (origin, direction; the w components are never read). The colour kernel
+// writes `colors`, the hits kernel the three other planes (nullptr: not
+// wanted), one 16-B record per ray each. Of LaunchParams the ray kernels read
+// `scene` and `layout` only: no view, no frame constants, no output pointer.
+struct RayTargets {
+    const float4 *rays;
+    float4 *colors;   // (r, g, b, 0)
+    int4 *hits;       // rt_hit
+    float4 *normals;  // (n, 0); a miss (0, 0, 0, 0)
+    float4 *points;   // (p, 0); a miss (0, 0, 0, 0)
+    int64_t n_rays;   // 1..RT_MAX_RAYS
+    int32_t flags;    // RT_HITS_*
+    int32_t cull;     // RT_OPT_CULLING
+};
+static_assert(sizeof(RayTargets) == 56 && sizeof(LaunchParams) + sizeof(RayTargets) <= 6144, "kernel argument block");
+// A caller's ray may walk the approximate pre-tests of the closest-hit search
+// (the sphere BVH's node test) only while its origin lies within this many
+// units of the world's origin on every axis: rt_kernel.hip node_hit derives
+// the bound (the node test stays conservative to about 4,000 units; a quarter
+// of that is taken). And only while its direction is a unit vector up to
+// rounding, | |d|^2 - 1 | <= 2^-19: its reflection and refraction children
+// keep its length, and the origin-sphere lists' stored distance bounds are
+// compared with their ray parameters (rt_scene.cpp origin_lists_range allows
+// 1e-5 of the length; 2^-20 here, and about 1e-6 more over nine bounces). A
+// wave that holds a ray outside either runs with culling off, for the ray's
+// whole tree and its shading: every box and every sphere tested exactly,
+// which the closest hit and the shadow queries do not notice.
+// (-DRT_RAY_NEAR_ORIGIN=1e30f: a probe build whose far origins walk the BVH, to
+// see tests/test_gpu_rays.py's far set fail; never the product build)
+#ifndef RT_RAY_NEAR_ORIGIN
+#define RT_RAY_NEAR_ORIGIN 1024.0f
+#endif
+constexpr float kRayNearOrigin = RT_RAY_NEAR_ORIGIN;
+constexpr float kRayUnitDir = 0x1p-19f;
+// rays_kernel<max_depth> over o.n_rays rays (colours), 256 rays per work-group.
+hipError_t launch_rays(LaunchParams &p, const RayTargets &o, int max_depth, hipStream_t stream);
+// ray_hits_kernel over o.n_rays rays (hits, normals, points).
+hipError_t launch_ray_hits(LaunchParams &p, const RayTargets &o, hipStream_t stream);
+// view_rays_kernel: the camera rays of p.view[0] for rows [p.row_begin,
+// p.row_begin + p.n_rows) of a p.width x p.height frame, in pixel order.
+hipError_t launch_view_rays(const LaunchParams &p, float4 *rays, hipStream_t stream);
 
 // rt_api.cpp
 void set_error(const std::string &msg);
@@ -850,6 +893,10 @@ struct rt_context {
     size_t staging_px = 0;
     float4 *hits_staging = nullptr;  // the same for rt_render_hits*: three planes of hits_staging_px records
     size_t hits_staging_px = 0;
+    // the same for rt_trace_rays / rt_view_rays with host buffers: the rays (two
+    // 16-B units each) and the wanted planes behind them, rays_staging_units units
+    float4 *rays_staging = nullptr;
+    size_t rays_staging_units = 0;
     int aa_queued = 1;  // RT_OPT_AA_QUEUED
     // adaptive anti-aliasing (rt_render_aa*): one grow-only device allocation
     // [queue counters][masks][lists][refined plane of a host-destination call],

@@ -527,6 +527,11 @@ __device__ __forceinline__ float box_t(const BoxRec &b, v3 rs, v3 rd, bool insid
 // included). Anything else — a tiny or non-finite direction component, a
 // non-finite distance — is "may hit", and the exact test decides. So a culled
 // lane is one whose exact test misses: bit-identical results.
+// The ray's origin does not enter the bound: rs is the box-local origin the
+// exact test itself computes and the numerators are the exact test's floats,
+// so a caller's ray (rt_trace_rays) of any finite origin is covered as it
+// stands. (A |d| above 2^126, where v_rcp flushes to zero: q' = 0 on every
+// axis, no miss condition holds, "may hit".)
 __device__ __forceinline__ bool slab_may_hit(const BoxRec &b, v3 rs, v3 rd, float t_max) {
     const bool ok = fabsf(rd.x) >= 0x1p-60f && fabsf(rd.y) >= 0x1p-60f && fabsf(rd.z) >= 0x1p-60f;
     const float ix = __builtin_amdgcn_rcpf(rd.x), iy = __builtin_amdgcn_rcpf(rd.y), iz = __builtin_amdgcn_rcpf(rd.z);
@@ -693,6 +698,28 @@ __device__ __forceinline__ void test_sphere(const Scene &S, int s, v3 start, v3 
 // that margin for origins within 20 units of the centre, so no extra slack
 // is needed: a node whose spheres the exact test could hit before t_limit
 // always passes (tn <= t of the hit < t_limit, tf >= it > 0).
+// A caller's ray (rt_trace_rays) may start anywhere. Per axis, with id =
+// rcp(d) (1 + e1), |e1| <= 2^-23, oid = fl(o id) and one rounding of the fma,
+// the computed distance is t (1 + e1) - (o / d) e2 (1 + e1) rounded once,
+// |e2| <= 2^-24: off by at most 1.5 * 2^-23 |t| + 2^-24 |o / d|. In units of
+// position (times |d|), with |t d| = |x - o| <= |o| + |x| for a slab plane x:
+// 1.8e-7 (|o| + |x|) + 6e-8 |o| against the margin 1e-3 + 1e-4 |x|. The |x|
+// terms never meet (1.8e-7 against 1e-4); the |o| terms reach 1e-3 at
+// |o| = 4,100. The ray kernels walk the BVH for |o| <= kRayNearOrigin = 1024
+// per axis (2.5e-4, a quarter of the margin) and unit directions (kRayUnitDir,
+// rt_internal.h; so no |d| that v_rcp would flush) and send every other wave
+// to the exhaustive branch of closest_impl (S.cull = 0), where each sphere
+// takes the exact test. A
+// direction component of zero or below 1e-30 takes safe_rcp's +-1e30: the
+// plane distances become (x - o) 1e30 -+ 2^-24 |o| 1e30, of the right sign
+// while the margin exceeds 2^-24 |o|, which the same bound covers. A NaN
+// anywhere fails the comparisons below (the node is skipped, the walk goes on
+// along its miss link).
+// Termination of the walks that use this test: a walk follows one depth-first
+// order of the tree (the skip links, or its octant's link words, fixed before
+// the walk from the direction's sign bits): a hit's link and a miss's link both
+// name a node later in that order or the end, so a lane visits each node at
+// most once whatever the test answers.
 struct RayInv {
     v3 oid, id;  // o * id, 1 / d (approximate)
 };
@@ -907,6 +934,14 @@ __device__ __forceinline__ Hit closest(const Scene &S, const Ray &r, bool valid,
 // / row from the hardware's face coordinates over it. Approximate
 // arithmetic: the host's texel cones carry a margin far above its error. A
 // direction without a usable largest component gets every sphere.
+// Its uses and a caller's ray (rt_trace_rays): the shadow queries look up the
+// direction from a light to the shaded point (phong_impl, hits_wave_tile: a
+// function of the hit point alone, which lies on a surface of the scene
+// wherever the ray came from; so are the cones, planes and masks those
+// queries read); the origin-sphere lists look up the direction of a ray that
+// starts on a sphere (closest_impl, origin >= 0), which a caller's ray never
+// does (origin = -1: the walk or the exhaustive tests). Neither sees the
+// caller's origin.
 // Texel of direction u, or -1.
 __device__ __forceinline__ int direction_texel(int n, v3 u) {
     // the cube-map instructions: face id (+x, -x, +y, -y, +z, -z; z, then y
@@ -1607,7 +1642,15 @@ struct Frames {
 // `emit(value)` receives each lane's colour when its tree is finished (the
 // lane then rides along with valid = false): the caller stores the pixel
 // there, so no result registers stay live through the rest of the walk.
-template <int kDepth, class Emit>
+// kCamera false (the ray kernels, rt_trace_rays): the first ray is a caller's,
+// of any origin, and takes the secondary rays' instantiations as every other
+// ray of the tree does.
+// Termination, whatever a lane's ray holds (a zero direction after total
+// internal reflection, a caller's non-finite components): an iteration either
+// pushes a node (level + 1 <= kDepth), starts a pending refraction child (once
+// per node) or finishes the lane, so a lane makes at most 2^(kDepth + 1) - 1
+// iterations; `hit`, `sr` and `st` are plain comparisons (false on NaN).
+template <int kDepth, bool kCamera = true, class Emit>
 __device__ __forceinline__ void trace_tree(const Scene &S, Ray ray, bool active, Emit &&emit) {
     const v3 black = mk(0.0f, 0.0f, 0.0f);
     Frames<kDepth> F;
@@ -1621,9 +1664,9 @@ __device__ __forceinline__ void trace_tree(const Scene &S, Ray ray, bool active,
     while (wave_any(!done)) {
         RT_STAT(11, (threadIdx.x & 63) == __builtin_ctzll(__ballot(1)));
         const bool valid = !done;
-        const bool primary = first;
-        // (origin lists: depth >= 2 only, S.olist)
-        const Hit h = first ? closest<true>(S, ray, valid) : closest<false>(S, ray, valid, kDepth >= 2 ? (lv >> 8) - 1 : -1);
+        const bool primary = kCamera && first;
+        // (origin lists: depth >= 2 only, S.olist; a caller's ray starts with lv = 0: no origin sphere)
+        const Hit h = primary ? closest<true>(S, ray, valid) : closest<false>(S, ray, valid, kDepth >= 2 ? (lv >> 8) - 1 : -1);
         first = false;
         const bool hit = valid && h.obj >= 0;
         const Collision c = primary ? resolve<true>(S, ray, h, hit) : resolve<false>(S, ray, h, hit);
@@ -2669,6 +2712,211 @@ void hits_kernel(LaunchParams p, HitTargets o) {
     hits_wave_tile(p, o, S, V, own_wx, own_wy, own, own_ray);
 }
 
+// ---- ray queries (rt_trace_rays, rt_view_rays) -------------------------------
+// A buffer of caller-supplied rays instead of a view: lane i of work-group g
+// owns ray 256 g + i, loads it with two 16-B loads while the scene is staged
+// (hits_kernel's prologue without the view's records: no frame constants, so
+// sph_cam, sph_px and box_cam are null, and nothing on the path reads them:
+// closest<false>, resolve<false> compute the origin's terms per ray, as every
+// secondary ray's do) and stores one 16-B record per plane. The scene is read
+// as the general kernels read it (kShape 0: every feature at run time, S.room
+// = 0), culling from the context. Consecutive rays share a wave, so whatever
+// coherence the caller's order has is the wave's; there are no pixel
+// footprints to cull with.
+//
+// Origins and directions outside the approximate pre-tests' proofs
+// (rt_internal.h kRayNearOrigin, kRayUnitDir; node_hit derives the first):
+// a wave that holds such a ray runs with S.cull = 0, the branch of
+// closest_impl and occluded_impl that tests every box and every sphere
+// exactly. The closest hit is order-independent (closer()'s explicit index
+// tie-break) and the shadow queries are any-hit, so the answers are those of
+// the culled paths (what RT_OPT_CULLING 0 shows for every render). The choice
+// is made once per wave, for the whole tree: a far ray's hit point carries an
+// error of about 2^-23 of the origin's distance, which the secondary rays'
+// structures were not derived for either. Every other wave's hit points lie on
+// the scene's surfaces as a camera ray's do, and what depends on the hit point
+// alone (shadow masks, cones, planes, the children's origin-sphere lists) is
+// reached as it is from a render.
+//
+// A lane whose ray holds a non-finite component: its wave is "far" (the
+// comparisons below fail on NaN and on inf), every loop it then runs is a
+// counted loop over the scene's boxes, spheres and lights, and the tree walk is
+// bounded by its depth (trace_tree), so it ends with some record of its own
+// and touches no memory but its own 16-B slots.
+template <bool kDeep>
+__device__ __forceinline__ Scene ray_scene(const LaunchParams &p, const float4 *lds, const float4 *blob, int cull) {
+    const SceneLayout &L = p.layout;
+    Scene S;
+    S.sph = lds + L.off_spheres;
+    S.smeta = reinterpret_cast<const int4 *>(lds + L.off_smeta);
+    S.sph_cam = nullptr;  // (no view: never read, every instantiation on the path is <false>)
+    S.cam_terms = 0;
+    S.sph_px = nullptr;
+    S.box = reinterpret_cast<const BoxRec *>(lds + L.off_boxes);
+    S.box_cam = nullptr;
+    S.mat = reinterpret_cast<const MatRec *>(lds + L.off_mats);
+    S.light = reinterpret_cast<const LightRec *>(lds + L.off_lights);
+    S.lm = reinterpret_cast<const LightMatRec *>(lds + L.off_lightmat);
+    S.bvh = lds + L.off_bvh;
+    S.blink = reinterpret_cast<const uint32_t *>(lds + L.off_blink);
+    S.cone = L.off_cone >= 0 ? reinterpret_cast<const ShadowCone *>(lds + L.off_cone) : nullptr;
+    S.dmask = L.off_dmask >= 0 ? reinterpret_cast<const char *>(lds + L.off_dmask) : nullptr;
+    S.dmask_n = L.dmask_n;
+    S.dmask_bytes = L.dmask_bytes;
+    S.dmask_box = L.dmask_box;
+    S.cbplane = cull && L.off_bplane >= 0 ? (const __attribute__((address_space(4))) float4 *)(blob + L.off_bplane) : nullptr;
+    // (as render_kernel: the wide masks and the lists at the recursive depths only)
+    S.gmask = kDeep && L.off_gmask >= 0 ? reinterpret_cast<const uint64_t *>(blob + L.off_gmask) : nullptr;
+    S.gwords = L.gmask_words;
+    S.glist = S.gmask && L.off_glist >= 0 ? reinterpret_cast<const uint4 *>(blob + L.off_glist) : nullptr;
+    S.olist = kDeep && L.off_olist >= 0 ? reinterpret_cast<const uint4 *>(blob + L.off_olist) : nullptr;
+    S.cbox = (const __attribute__((address_space(4))) BoxRec *)(blob + L.off_boxes);
+    S.clight = (const __attribute__((address_space(4))) LightRec *)(blob + L.off_lights);
+#ifdef RT_UNIFORM_MAT
+    S.cmat = (const __attribute__((address_space(4))) MatRec *)(blob + L.off_mats);
+    S.clm = (const __attribute__((address_space(4))) LightMatRec *)(blob + L.off_lightmat);
+#endif
+    S.nbvh = L.n_bvh;
+    S.ns = L.n_spheres;
+    S.nb = L.n_boxes;
+    S.nl = L.n_lights;
+    S.nm = L.n_mats;
+    S.cull = cull;
+    S.room = 0;
+    S.room_fast = 0;
+    S.tx0 = S.tx1 = S.ty0 = S.ty1 = 0;
+    return S;
+}
+// The prologue both ray kernels share: the lane's ray requested, the scene
+// blob staged into LDS behind one barrier. `at`: the lane's ray (and record)
+// index; a lane past the last ray rides along with a fixed unit ray.
+__device__ __forceinline__ Ray ray_prologue(const LaunchParams &p, const RayTargets &o, float4 *lds, size_t &at,
+                                            bool &active) {
+    __builtin_amdgcn_s_setprio(1);
+    const float4 *blob = static_cast<const float4 *>(p.scene);
+    const int tid = threadIdx.x;
+    float4 first = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (tid < p.layout.blob_units) first = blob[tid];
+    at = static_cast<size_t>(blockIdx.x) * kThreads + static_cast<size_t>(tid);
+    active = at < static_cast<size_t>(o.n_rays);
+    // (the ray's two loads while the staging loads are in flight)
+    float4 ro = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rd = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
+    if (active) {
+        ro = o.rays[2 * at];
+        rd = o.rays[2 * at + 1];
+    }
+    if (tid < p.layout.blob_units) lds[tid] = first;
+    for (int i = tid + kThreads; i < p.layout.blob_units; i += kThreads) lds[i] = blob[i];
+    __syncthreads();
+    __builtin_amdgcn_s_setprio(0);
+    return Ray{mk(ro.x, ro.y, ro.z), mk(rd.x, rd.y, rd.z)};
+}
+// The wave holds a ray outside the pre-tests' proofs: culling off for the wave.
+__device__ __forceinline__ void ray_wave_range(Scene &S, const Ray &r, bool active) {
+    const bool near = fabsf(r.start.x) <= kRayNearOrigin && fabsf(r.start.y) <= kRayNearOrigin &&
+                      fabsf(r.start.z) <= kRayNearOrigin && fabsf(dot(r.dir, r.dir) - 1.0f) <= kRayUnitDir;  // (NaN fails)
+    if (wave_any(active && !near)) {
+        S.cull = 0;
+        S.cbplane = nullptr;
+    }
+}
+
+// Colours: trace0's body on the loaded ray at depth 0 (its per-wave early out
+// included), the tree walk above it.
+template <int kDepth>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RT_WAVES_PER_EU(kDepth, 0))))
+void rays_kernel(LaunchParams p, RayTargets o) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds[];
+    size_t at;
+    bool active;
+    const Ray ray = ray_prologue(p, o, lds, at, active);
+    if (!wave_any(active)) return;  // (a wave past the last ray; the barrier is behind it)
+    Scene S = ray_scene<(kDepth >= 2)>(p, lds, static_cast<const float4 *>(p.scene), o.cull);
+    ray_wave_range(S, ray, active);
+    if constexpr (kDepth > 0) {
+        trace_tree<kDepth, false>(S, ray, active,
+                                  [&](v3 col) { o.colors[at] = make_float4(col.x, col.y, col.z, 0.0f); });
+    } else {
+        const v3 black = mk(0.0f, 0.0f, 0.0f);
+        const Hit h = closest<false>(S, ray, active);
+        const bool hit = active && h.obj >= 0;
+        v3 col = black;
+        if (wave_any(hit)) {  // (per-wave early out, as trace0)
+            const Collision c = resolve<false>(S, ray, h, hit);
+            col = sel(hit, phong(S, ray, c, hit), black);
+        }
+        if (active) o.colors[at] = make_float4(col.x, col.y, col.z, 0.0f);
+    }
+}
+
+// Hit records: hits_wave_tile's body on the loaded ray (the dead lights' query
+// as there: a copy of the scene with nothing culled).
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RT_WAVES_PER_EU(0, 0))))
+void ray_hits_kernel(LaunchParams p, RayTargets o) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds[];
+    size_t at;
+    bool active;
+    const Ray ray = ray_prologue(p, o, lds, at, active);
+    if (!wave_any(active)) return;
+    Scene S = ray_scene<false>(p, lds, static_cast<const float4 *>(p.scene), o.cull);
+    ray_wave_range(S, ray, active);
+    const Hit h = closest<false>(S, ray, active);
+    const bool hit = active && h.obj >= 0;
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!wave_any(hit)) {  // per-wave early out: misses
+        if (active) {
+            if (o.hits) o.hits[at] = make_int4(-1, 0, 0, -1);
+            if (o.normals) o.normals[at] = zero;
+            if (o.points) o.points[at] = zero;
+        }
+        return;
+    }
+    const Collision c = resolve<false>(S, ray, h, hit);
+    uint32_t shadow = 0u;
+    if ((o.flags & RT_HITS_SHADOW) != 0 && o.hits) {
+        Scene U = S;  // a dead light's query: nothing culled
+        U.cull = 0;
+        U.cbplane = nullptr;
+        const v3 start = add(c.p, muls(c.n, 0.01f));  // (:808)
+        int slot = -1;  // index among the live lights (direction masks)
+        for (int j = 0; j < S.nl; ++j) {
+            const LightRec L = cload(S.clight + j);
+            const v3 lpos = mk(L.pos[0], L.pos[1], L.pos[2]);
+            const v3 sdir = sub(lpos, c.p);  // (:809)
+            bool shadowed;
+            if (L.dead != 0.0f) {
+                shadowed = occluded(U, start, sdir, c.p, lpos, j, 0, 0u, hit);
+            } else {
+                ++slot;
+                uint64_t smask = 0u;
+                if (S.dmask)
+                    smask = direction_mask(S.dmask + slot * 6 * S.dmask_n * S.dmask_n * S.dmask_bytes, S.dmask_n,
+                                           S.dmask_bytes, muls(sdir, -1.0f), S.ns + (S.dmask_box ? S.nb : 0));
+                shadowed = occluded(S, start, sdir, c.p, lpos, j, slot, smask, hit);
+            }
+            if (hit && shadowed) shadow |= 1u << j;
+        }
+    }
+    if (!active) return;
+    if (o.hits)
+        o.hits[at] = hit ? make_int4(h.obj, __float_as_int(h.t), static_cast<int>(shadow), c.material)
+                         : make_int4(-1, 0, 0, -1);
+    if (o.normals) o.normals[at] = hit ? make_float4(c.n.x, c.n.y, c.n.z, 0.0f) : zero;
+    if (o.points) o.points[at] = hit ? make_float4(c.p.x, c.p.y, c.p.z, 0.0f) : zero;
+}
+
+// rt_view_rays: the camera rays of view 0, camera_ray's text with no jitter,
+// one thread per pixel of the launch's rows in rt_render's pixel order.
+__global__ __launch_bounds__(kThreads) void view_rays_kernel(LaunchParams p, float4 *rays) {
+    const size_t at = static_cast<size_t>(blockIdx.x) * kThreads + threadIdx.x;
+    if (at >= static_cast<size_t>(p.n_rows) * static_cast<size_t>(p.width)) return;
+    const int local_row = static_cast<int>(at / static_cast<size_t>(p.width));
+    const int x = static_cast<int>(at - static_cast<size_t>(local_row) * static_cast<size_t>(p.width));
+    const Ray r = camera_ray(p, p.view[0], x, p.row_begin + local_row, 0.0f, 0.0f);
+    rays[2 * at] = make_float4(r.start.x, r.start.y, r.start.z, 0.0f);
+    rays[2 * at + 1] = make_float4(r.dir.x, r.dir.y, r.dir.z, 0.0f);
+}
+
 // ---- adaptive anti-aliasing (rt_render_aa*) ---------------------------------
 // Three launches on the call's stream: the base frame (a render like any
 // other, launch_render), the edge kernel over the frame just written, and the
@@ -3069,6 +3317,46 @@ hipError_t launch_hits(LaunchParams &p, const HitTargets &o, hipStream_t stream)
 }
 
 namespace {
+using RaysFn = void (*)(LaunchParams, RayTargets);
+constexpr RaysFn kRays[RT_MAX_DEPTH + 1] = {&rays_kernel<0>, &rays_kernel<1>, &rays_kernel<2>, &rays_kernel<3>,
+                                            &rays_kernel<4>, &rays_kernel<5>, &rays_kernel<6>, &rays_kernel<7>,
+                                            &rays_kernel<8>, &rays_kernel<9>};
+// One work-group per 256 rays; LDS: the blob's staged part (no view records).
+hipError_t launch_ray_fn(const void *fn, LaunchParams &p, const RayTargets &o, hipStream_t stream) {
+    if (o.n_rays <= 0 || o.n_rays > RT_MAX_RAYS) return hipErrorInvalidValue;
+    p.sched = nullptr;
+    RayTargets targets = o;
+    void *args[] = {&p, &targets};
+    const dim3 grid(static_cast<unsigned>((o.n_rays + kThreads - 1) / kThreads), 1, 1);  // <= 2^20
+    const hipError_t e = hipLaunchKernel(fn, grid, dim3(kThreads), args,
+                                         static_cast<size_t>(p.layout.blob_units) * sizeof(float4), stream);
+    (void)hipGetLastError();  // (e is the launch's own status; no sticky error for a later check)
+    return e;
+}
+}  // namespace
+
+hipError_t launch_rays(LaunchParams &p, const RayTargets &o, int max_depth, hipStream_t stream) {
+    if (max_depth < 0 || max_depth > RT_MAX_DEPTH || !o.colors) return hipErrorInvalidValue;
+    return launch_ray_fn(reinterpret_cast<const void *>(kRays[max_depth]), p, o, stream);
+}
+
+hipError_t launch_ray_hits(LaunchParams &p, const RayTargets &o, hipStream_t stream) {
+    if (!o.hits && !o.normals && !o.points) return hipErrorInvalidValue;
+    return launch_ray_fn(reinterpret_cast<const void *>(&ray_hits_kernel), p, o, stream);
+}
+
+hipError_t launch_view_rays(const LaunchParams &p, float4 *rays, hipStream_t stream) {
+    LaunchParams q = p;
+    void *args[] = {&q, &rays};
+    const size_t n = static_cast<size_t>(p.n_rows) * static_cast<size_t>(p.width);  // <= 2^32
+    const dim3 grid(static_cast<unsigned>((n + kThreads - 1) / kThreads), 1, 1);
+    const hipError_t e =
+        hipLaunchKernel(reinterpret_cast<const void *>(&view_rays_kernel), grid, dim3(kThreads), args, 0, stream);
+    (void)hipGetLastError();
+    return e;
+}
+
+namespace {
 using AaRefineFn = void (*)(LaunchParams, AaTargets);
 // the queued kernel of every depth, and the tiled ones of depths 0-1
 constexpr AaRefineFn kAaRefine[RT_MAX_DEPTH + 1] = {
@@ -3277,6 +3565,11 @@ hipError_t allow_large_lds(size_t bytes) {
         (void)hipFuncSetAttribute(row.fn(), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hits_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               static_cast<int>(bytes));
+    for (const RaysFn fn : kRays)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  static_cast<int>(bytes));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ray_hits_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
     for (const AaRefineFn fn : kAaRefine)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   static_cast<int>(bytes));

@@ -68,6 +68,13 @@ def kernel_name(mangled):
         return "aa_refine_kernel<%s,%s>" % (m.group(1), "true" if m.group(2) == "1" else "false")
     if re.search(r"\d+aa_edge_kernelE", mangled):
         return "aa_edge_kernel"
+    m = re.search(r"\d+rays_kernelILi(\d)EE", mangled)  # ray queries (rt_trace_rays; not rows either): depth
+    if m:
+        return "rays_kernel<%s>" % m.group(1)
+    if re.search(r"\d+ray_hits_kernelE", mangled):
+        return "ray_hits_kernel"
+    if re.search(r"\d+view_rays_kernelE", mangled):
+        return "view_rays_kernel"
     return mangled
 
 
@@ -108,7 +115,8 @@ def resources(so):
     for r in out.values():
         if "vgpr" in r:
             r["waves_per_simd"] = min(8, 512 // max(8, -(-r["vgpr"] // 8) * 8))
-    return {k: v for k, v in out.items() if k.startswith(("render_kernel", "animate_kernel", "hits_kernel", "aa_"))}
+    return {k: v for k, v in out.items() if k.startswith(("render_kernel", "animate_kernel", "hits_kernel", "aa_", "rays_kernel", "ray_hits_kernel",
+                                                         "view_rays_kernel"))}
 
 
 def texts(so):
@@ -184,6 +192,13 @@ TABLE = [
     ("depth 2, general", "render_kernel<2,false,false>"),
     ("depth 4, config 4 (room, wide masks, origin lists)", "render_kernel<4,false,false,48>"),
     ("depth 4, general", "render_kernel<4,false,false>"),
+    ("ray queries (rt_trace_rays), colours at depth 0", "rays_kernel<0>"),
+    ("ray queries, depth 1", "rays_kernel<1>"),
+    ("ray queries, depth 2", "rays_kernel<2>"),
+    ("ray queries, depth 4", "rays_kernel<4>"),
+    ("ray queries, depth 9", "rays_kernel<9>"),
+    ("ray queries, the hit records (hits_kernel's body on a loaded ray)", "ray_hits_kernel"),
+    ("rt_view_rays (camera_ray into the ray buffer)", "view_rays_kernel"),
     ("the animate kernel (one work-group per frame ahead of an animated render, rt_anim.hip), boxes only",
      "animate_kernel<false>"),
     ("the animate kernel with the sphere phases (scenes with moving spheres)", "animate_kernel<true>"),
