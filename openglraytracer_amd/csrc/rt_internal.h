@@ -862,8 +862,8 @@ int check_render_args(const rt_context *ctx, const rt_scene *scene, int width, i
 // to the caller) and, in h, the host's side of the launch decisions
 LaunchParams base_params(const rt_context *ctx, const rt_scene *scene, const rt_view *views, int n_views,
                          int width, int height, LaunchHost &h);
-// launch on `stream` with the context's queue slot and kernel-time events
-int launch(rt_context *ctx, LaunchParams &p, const LaunchHost &h, int max_depth, hipStream_t stream);
+// launch on `stream` with the context's queue slot; span: between kernel-time events of its own
+int launch(rt_context *ctx, LaunchParams &p, const LaunchHost &h, int max_depth, hipStream_t stream, bool span = true);
 // Before a render at max_depth: a scene that reads origin-sphere lists at
 // this depth (max_depth >= 2, RT_OPT_ORIGIN_LISTS on, 33-256 spheres) gets
 // them built and appended to its device blob the first time (the region past
@@ -882,6 +882,17 @@ int launch_scene(rt_context *ctx, const rt_scene *scene, LaunchParams &p, const 
                  hipStream_t stream);
 // bytes per pixel of a surface format (RT_OUTPUT_*)
 inline size_t surface_bytes(int fmt) { return fmt == RT_OUTPUT_RGBA8 ? 4 : (fmt == RT_OUTPUT_RGB32F ? 12 : 16); }
+// A grow-only device buffer of `units` units of `unit` bytes: reserve frees and
+// allocates anew when it has to grow (hipFree waits for the device, so an
+// earlier call's use of the old block is over) and never shrinks (rt_api.cpp).
+struct DeviceBuffer {
+    size_t unit = sizeof(float4);
+    void *ptr = nullptr;
+    size_t units = 0;
+    float4 *records() const { return static_cast<float4 *>(ptr); }
+    int reserve(size_t n, const char *what);  // what: hip_fail's label
+    void release();
+};
 
 }  // namespace rtamd
 
@@ -889,21 +900,18 @@ struct rt_context {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float4 *staging = nullptr;  // device buffer for host-destination renders
-    size_t staging_px = 0;
-    float4 *hits_staging = nullptr;  // the same for rt_render_hits*: three planes of hits_staging_px records
-    size_t hits_staging_px = 0;
+    rtamd::DeviceBuffer staging;       // host-destination renders: a float4 per pixel (serves every format)
+    rtamd::DeviceBuffer hits_staging;  // the same for rt_render_hits*: three planes of a record per pixel
     // the same for rt_trace_rays / rt_view_rays with host buffers: the rays (two
-    // 16-B units each) and the wanted planes behind them, rays_staging_units units
-    float4 *rays_staging = nullptr;
-    size_t rays_staging_units = 0;
+    // 16-B units each) and the wanted planes behind them
+    rtamd::DeviceBuffer rays_staging;
     int aa_queued = 1;  // RT_OPT_AA_QUEUED
-    // adaptive anti-aliasing (rt_render_aa*): one grow-only device allocation
+    // adaptive anti-aliasing (rt_render_aa*): one device allocation, in bytes,
     // [queue counters][masks][lists][refined plane of a host-destination call],
     // sized for aa_slots mask slots (whole work-group tiles) and aa_px pixels; the
     // event follows the last call's use of it (and of `staging`), and the next
     // call's stream waits for it on the device
-    void *aa_scratch = nullptr;
+    rtamd::DeviceBuffer aa_scratch{1};
     size_t aa_slots = 0, aa_px = 0;
     hipEvent_t aa_done = nullptr;
     bool aa_used = false;

@@ -1,5 +1,5 @@
 """Kernel time of the primary-hit kernel against the general depth-0 render:
-    python tools/hits_time.py [--out profiles/NAME.log]
+    python tools/hits_time.py [--lib PATH] [--out profiles/NAME.log]
 
 Config 2's scene (bench_objects(16)), 1920 x 1080, one process, device
 buffers. The median of 21 rt_last_kernel_ms readings (HIP events around the
@@ -27,7 +27,10 @@ W, H, WARMUP, READINGS = 1920, 1080, 3, 21
 
 
 def main():
-    out_path = sys.argv[2] if len(sys.argv) > 2 and sys.argv[1] == "--out" else None
+    opt = lambda name: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else None  # noqa: E731
+    out_path = opt("--out")
+    if opt("--lib"):  # another build of the library (tools/ablate.sh rev REV), for A/B rounds in one GPU call
+        rt.LIB_PATH = os.path.abspath(opt("--lib"))
     ctx = rt.Context(0)
     sc = rt.Scene(ctx, scenes.bench_objects(16))
     view = rt.make_view(None, 0.0)

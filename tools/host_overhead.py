@@ -1,6 +1,7 @@
 """Host cost of one render call (tiny frame: the GPU is never the bottleneck)
 and the back-to-back frame rate at 1920x1080, with and without the context's
-per-launch timing events (development probe)."""
+per-launch timing events (development probe). --lib PATH: another build of the
+library (tools/ablate.sh rev REV), for A/B rounds in one GPU call."""
 import ctypes as C
 import os
 import sys
@@ -11,6 +12,8 @@ sys.path.insert(0, ROOT)
 import torch
 import openglraytracer_amd as rt
 
+if "--lib" in sys.argv:
+    rt.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 ctx = rt.Context(0)
 sc = rt.Scene(ctx, rt.bench_objects(16, 0))
 out = torch.empty((1080, 1920, 4), dtype=torch.float32, device="cuda")

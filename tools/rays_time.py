@@ -1,5 +1,5 @@
 """Kernel time of the ray queries against the renders of the same frame:
-    python tools/rays_time.py [--out profiles/NAME.log]
+    python tools/rays_time.py [--lib PATH] [--out profiles/NAME.log]
 
 One process, device buffers, the rays of the orbit view at t = 0 as
 rt_view_rays writes them. The median of 21 rt_last_kernel_ms readings (HIP
@@ -80,7 +80,10 @@ def scene_cases(ctx, sc, w, h, depth, with_hits):
 
 
 def main():
-    out_path = sys.argv[2] if len(sys.argv) > 2 and sys.argv[1] == "--out" else None
+    opt = lambda name: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else None  # noqa: E731
+    out_path = opt("--out")
+    if opt("--lib"):  # another build of the library (tools/ablate.sh rev REV), for A/B rounds in one GPU call
+        rt.LIB_PATH = os.path.abspath(opt("--lib"))
     ctx = rt.Context(0)
     lines = ["# tools/rays_time.py: %s" % rt.lib().rt_version().decode(),
              "# median of %d rt_last_kernel_ms readings after %d warm-ups, the cases of a scene interleaved; "
