@@ -24,6 +24,9 @@ def lib():
                                     C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.oracle_render.restype = C.c_int
+        L.oracle_trace_rays.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.oracle_trace_rays.restype = C.c_int
         L.oracle_reference_objects.argtypes = [C.c_float, C.c_void_p]
         L.oracle_reference_camera.argtypes = [C.c_float, C.c_void_p]
         L.oracle_camera_matrices.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
@@ -73,6 +76,27 @@ def render(objects, width, height, max_depth=0, time=0.0, rows=None, probe=0, ma
                              max_depth, r0, r1, probe, threads, out.ctypes.data)
     if rc != 0:
         raise ValueError("oracle_render rejected its arguments")
+    return out
+
+
+def trace_rays(objects, rays, max_depth=0, probe=0, materials=None, lights=None, threads=0):
+    """Trace caller-supplied rays (an abi.RAY_DTYPE array or (n, 8) float32; the
+    direction as given, never normalised) -> float32 array (n, 4) of `probe`."""
+    materials = materials if materials is not None else reference_materials()
+    lights = lights if lights is not None else reference_lights()
+    rays = np.asarray(rays)
+    if rays.dtype.names is not None:
+        rays = np.ascontiguousarray(rays).view(np.float32)
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    objs = (Object * max(len(objects), 1))(*objects)
+    mats = (Material * len(materials))(*materials)
+    lts = (Light * max(len(lights), 1))(*lights)
+    out = np.zeros((len(rays), 4), np.float32)
+    rc = lib().oracle_trace_rays(C.addressof(objs), len(objects), C.addressof(mats), len(materials),
+                                 C.addressof(lts), len(lights), rays.ctypes.data, len(rays), max_depth, probe,
+                                 threads, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("oracle_trace_rays rejected its arguments")
     return out
 
 

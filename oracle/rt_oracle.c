@@ -987,6 +987,24 @@ int oracle_render_accumulate(const rt_object *objs, int n_objs, const rt_materia
     return 0;
 }
 
+/* One ray's probe value: the text oracle_render and oracle_trace_rays share.
+ * probe 0 colour; 1 the direction as given; 2 (object index, t, shadow mask);
+ * 3 closest-hit normal; 4 closest-hit point; a miss is zeros with object -1. */
+static v3 probe_ray(const scene_t *S, machine_t *M, ray_t r, int max_depth, int probe) {
+    if (probe == 0) return recursive_raytrace(S, M, r, max_depth);
+    if (probe == 1) return r.dir;
+    coll_t c = get_closest_collision(S, r);
+    if (probe == 2) {
+        float mask = 0.0f;
+        if (c.object_index != -1)
+            for (int j = 0; j < S->nl; j++)
+                if (in_shadow(S, c, &S->lights[j])) mask += (float)(1 << j);
+        return V3((float)c.object_index, c.t, mask);
+    }
+    if (c.object_index == -1) return V3(0, 0, 0);
+    return probe == 3 ? c.n : c.p;
+}
+
 /* :325-405 */
 int oracle_render(const rt_object *objs, int n_objs, const rt_material *mats, int n_mats,
                   const rt_light *lights, int n_lights, const rt_camera *cam_in, float time, int width,
@@ -1008,27 +1026,37 @@ int oracle_render(const rt_object *objs, int n_objs, const rt_material *mats, in
         machine_t *M = (machine_t *)malloc(sizeof(machine_t));
         int y = row0 + yy;
         for (int x = 0; x < width; x++) {
-            ray_t r = camera_ray(inv, &cam, x, y, hw, hh, 0.0f, 0.0f);
-            v3 col;
-            if (probe == 0) {
-                col = recursive_raytrace(&S, M, r, max_depth);
-            } else if (probe == 1) {
-                col = r.dir;
-            } else {
-                coll_t c = get_closest_collision(&S, r);
-                if (probe == 2) {
-                    float mask = 0.0f;
-                    if (c.object_index != -1)
-                        for (int j = 0; j < n_lights; j++)
-                            if (in_shadow(&S, c, &lights[j])) mask += (float)(1 << j);
-                    col = V3((float)c.object_index, c.t, mask);
-                } else if (c.object_index == -1) {
-                    col = V3(0, 0, 0);
-                } else {
-                    col = probe == 3 ? c.n : c.p;
-                }
-            }
+            v3 col = probe_ray(&S, M, camera_ray(inv, &cam, x, y, hw, hh, 0.0f, 0.0f), max_depth, probe);
             float *px = out + ((size_t)yy * width + x) * 4;
+            px[0] = col.x; px[1] = col.y; px[2] = col.z; px[3] = 0.0f;
+        }
+        free(M);
+    }
+    free(o);
+    return 0;
+}
+
+/* Caller-supplied rays through the same per-ray text as oracle_render: the
+ * direction is used as given, never normalised. */
+int oracle_trace_rays(const rt_object *objs, int n_objs, const rt_material *mats, int n_mats,
+                      const rt_light *lights, int n_lights, const float *rays, int n_rays, int max_depth,
+                      int probe, int n_threads, float *out) {
+    if (!objs || n_objs < 0 || !mats || n_mats <= 0 || (n_lights > 0 && !lights) || n_lights < 0 || n_rays < 0 ||
+        (n_rays > 0 && (!rays || !out)) || max_depth < 0 || probe < 0 || probe > 4)
+        return -1;
+    obj_t *o = prepare_objects(objs, n_objs, mats, n_mats);
+    if (!o) return -1;
+    scene_t S = {o, n_objs, lights, n_lights};
+#pragma omp parallel num_threads(n_threads > 0 ? n_threads : omp_get_max_threads())
+    {
+        machine_t *M = (machine_t *)malloc(sizeof(machine_t));
+#pragma omp for schedule(dynamic, 64)
+        for (int i = 0; i < n_rays; i++) {
+            ray_t r;
+            r.start = ld3(rays + (size_t)i * 8);
+            r.dir = ld3(rays + (size_t)i * 8 + 4);
+            v3 col = probe_ray(&S, M, r, max_depth, probe);
+            float *px = out + (size_t)i * 4;
             px[0] = col.x; px[1] = col.y; px[2] = col.z; px[3] = 0.0f;
         }
         free(M);

@@ -6,7 +6,7 @@ The grid (panorama_rays): column x looks at longitude 2 pi (x - W/2) / W, so
 column W/2 looks forward and column 0 straight back (the image wraps, no column
 twice); row y looks at latitude -pi/2 + pi y / (H - 1), so row 0 (the bottom
 row, as in every frame of this library) is the -z pole and row H - 1 the +z
-pole. Forward is +y with z up and +x to the right, the camera convention of
+pole, both exactly (0, 0, -1) and (0, 0, 1) in every column. Forward is +y with z up and +x to the right, the camera convention of
 rt_make_view at angles 0:
 
     d = (sin(lon) cos(lat), cos(lon) cos(lat), sin(lat))
@@ -32,8 +32,11 @@ def panorama_rays(origin, width, height):
     """The capture's rays, (height, width) of abi.RAY_DTYPE, row 0 the bottom row. No GPU."""
     lon = 2.0 * np.pi * (np.arange(width, dtype=np.float64) - width // 2) / width
     lat = -0.5 * np.pi + np.pi * np.arange(height, dtype=np.float64) / (height - 1) if height > 1 else np.zeros(1)
-    lon, lat = np.meshgrid(lon, lat)
-    d = np.stack([np.sin(lon) * np.cos(lat), np.cos(lon) * np.cos(lat), np.sin(lat)], -1)
+    cos_lat = np.cos(lat)
+    if height > 1:
+        cos_lat[0] = cos_lat[-1] = 0.0  # (cos(pi/2) in float64 is 6e-17: the pole rows are exactly (0, 0, -1) and (0, 0, 1))
+    lon, cos_lat = np.meshgrid(lon, cos_lat)
+    d = np.stack([np.sin(lon) * cos_lat, np.cos(lon) * cos_lat, np.repeat(np.sin(lat)[:, None], width, 1)], -1)
     d /= np.linalg.norm(d, axis=-1, keepdims=True)
     rays = np.zeros((height, width), abi.RAY_DTYPE)
     rays["origin"] = np.asarray(origin, np.float32)
