@@ -601,6 +601,35 @@ __host__ __device__ inline ChunkRange persistent_chunk(int c, int total, int wav
     }
     return c < total - start ? ChunkRange{start + c, start + c + 1} : ChunkRange{total, total};
 }
+// A chunk's items are consecutive wave tiles, view-major and row by row, so
+// they fall into runs: maximal stretches within one tile row of one view,
+// tiles (wx .. wx + n - 1, wy) of view z. What is the same for every tile of a
+// run (the view and its records, the row's terms, the store's row) the kernel
+// derives once per run; inside it only wx advances. (-DRT_TILE_RUNS=0: a
+// timing build that derives everything per tile, as before the runs.) The
+// one pair of functions the kernel and the host-only rt_debug_persistent_runs
+// call: the run that item t begins (the one division of a chunk), and the
+// run behind a run that ended at its row's last tile or at the chunk's end.
+// wtx x wty: the frame's wave tiles; `left`: the chunk's items from the run's
+// first on (> 0).
+#ifndef RT_TILE_RUNS
+#define RT_TILE_RUNS 1
+#endif
+constexpr bool kTileRuns = RT_TILE_RUNS != 0;
+struct TileRun {
+    int z, wy, wx, n;
+};
+__host__ __device__ inline TileRun persistent_first_run(int t, int left, int wtx, int wty) {
+    const int view_tiles = wtx * wty;
+    const int z = t / view_tiles, r = t - z * view_tiles;
+    const int wy = r / wtx, wx = r - wy * wtx;
+    return {z, wy, wx, left < wtx - wx ? left : wtx - wx};
+}
+// (the run before ended at its row's last tile: `left` > 0 items are still the chunk's)
+__host__ __device__ inline TileRun persistent_next_run(const TileRun &r, int left, int wtx, int wty) {
+    const bool last_row = r.wy + 1 == wty;
+    return {last_row ? r.z + 1 : r.z, last_row ? 0 : r.wy + 1, 0, left < wtx ? left : wtx};
+}
 // Automatic persistence (RT_OPT_PERSISTENT0 1) from this many wave tiles per
 // resident wave. Measured on config 2 at 1080p, tiled -> persistent per
 // launch: 9 views (36 tiles per wave) 270 -> 300 us, 16: 454 -> 467, 24:

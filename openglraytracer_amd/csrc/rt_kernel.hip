@@ -1919,15 +1919,35 @@ struct Pixel {
     int x, local_row, y;
     bool active;
 };
+// What the tiles of a run of a persistent launch share (render_persistent0,
+// rt_internal.h TileRun): derived at the run's head from the launch's
+// arguments and held in scalar registers, where a tile outside a run reads
+// the arguments (nullptr: no run). The scene's and the view's addresses and
+// the frame's size were live through a tile's body as it was, so holding them
+// from tile to tile adds no register to the body; the slot and the view's
+// frame in the output are the two that do.
+struct RunTerms {
+    float4 *slot;                                                   // the wave's view records in LDS (persistent_slot)
+    const __attribute__((address_space(4))) FrameView *view;        // the run's view in p.views_dev
+    const float4 *blob;                                             // p.scene
+    float4 *out;                                                    // the view's frame in p.out
+    int width, height;
+    // The room shapes (their instances have the registers for it; the others'
+    // took 8-12 B of scratch): a lane past the frame's right edge keeps its
+    // own row where the tiled launch gives it the tile's first. Such a lane
+    // stores nothing and its column is past the frame either way; the pixel's
+    // row then depends on the run alone and its conversion leaves the tile.
+    bool own_rows;
+};
 template <int kLaunch = 0>
-__device__ __forceinline__ Pixel wave_pixel(const LaunchParams &p, int wx, int wy) {
+__device__ __forceinline__ Pixel wave_pixel(const LaunchParams &p, int wx, int wy, const RunTerms *run = nullptr) {
     const int lane = threadIdx.x & 63;
     Pixel px;
     px.x = wx * 8 + (lane & 7);
     if constexpr ((kLaunch & kLaunchPlain) != 0) {  // rows 0..height of the frame, one slice
         px.local_row = wy * 8 + (lane >> 3);
-        px.active = px.x < p.width && px.local_row < p.height;
-        px.y = px.active ? px.local_row : wy * 8;
+        px.active = px.x < (run ? run->width : p.width) && px.local_row < (run ? run->height : p.height);
+        px.y = (run && run->own_rows ? px.local_row < run->height : px.active) ? px.local_row : wy * 8;
         return px;
     }
     px.local_row = p.slice_begin + wy * 8 + (lane >> 3);
@@ -1953,10 +1973,10 @@ constexpr bool kCameraProved(int depth, bool accum, int shape, int launch) {
 // (rt_scene.cpp camera_norm_range), so the direction is normalised without the vote.
 template <int kLaunch = 0, bool kProved = false>
 __device__ __forceinline__ Ray camera_ray(const LaunchParams &p, const FrameView &V, int x, int y, float jx,
-                                          float jy) {
+                                          float jy, const RunTerms *run = nullptr) {
     // (a plain launch: at least 2 x 2 pixels and the host's short-division proof hold)
     constexpr bool kPlain = (kLaunch & kLaunchPlain) != 0;
-    const int hw = p.width / 2, hh = p.height / 2;
+    const int hw = (run ? run->width : p.width) / 2, hh = (run ? run->height : p.height) / 2;
     const float *M = V.unproj;  // column-major
     // x - hw + jx is +0 or a multiple of 2^-24 of magnitude <= 2^16: the
     // short division by the (uniform) W/2, H/2 >= 1 is the correctly rounded
@@ -2014,7 +2034,8 @@ __device__ __forceinline__ Ray camera_ray(const LaunchParams &p, const FrameView
 // path computes it while the scene is staged), or nullptr.
 template <int kDepth, bool kAccum, int kShape, int kLaunch = 0>
 __device__ __forceinline__ void render_wave_tile(const LaunchParams &p, Scene S, const FrameView &V, int wx, int wy,
-                                                 int z, const Pixel &px, const Ray &pre, bool have_pre) {
+                                                 int z, const Pixel &px, const Ray &pre, bool have_pre,
+                                                 const RunTerms *run = nullptr) {
     S.cull = V.cull;
     S.room = 0;
     S.cam_terms = kLeanViews(kShape) ? 0 : 1;
@@ -2074,10 +2095,10 @@ __device__ __forceinline__ void render_wave_tile(const LaunchParams &p, Scene S,
         }
     }
     float4 *out = p.out + static_cast<size_t>(z) * p.n_rows * p.width;
-    const uint32_t idx = static_cast<uint32_t>(local_row) * static_cast<uint32_t>(p.width) + static_cast<uint32_t>(x);
+    const uint32_t idx = static_cast<uint32_t>(local_row) * static_cast<uint32_t>(run ? run->width : p.width) + static_cast<uint32_t>(x);
 
     if constexpr (!kAccum) {
-        const Ray ray = have_pre ? pre : camera_ray<kLaunch, kCameraProved(kDepth, kAccum, kShape, kLaunch)>(p, V, x, y, 0.0f, 0.0f);
+        const Ray ray = have_pre ? pre : camera_ray<kLaunch, kCameraProved(kDepth, kAccum, kShape, kLaunch)>(p, V, x, y, 0.0f, 0.0f, run);
 #if defined(RT_ABLATE_RAYGEN)
         (void)ray;
         const v3 col = mk(float(x), float(y), 0.0f);
@@ -2099,7 +2120,9 @@ __device__ __forceinline__ void render_wave_tile(const LaunchParams &p, Scene S,
         const v3 col = trace0<kRoom>(S, ray, active);
 #endif
         RT_CYC_AFTER(kCycStore, col.x);
-        if (active) store_pixel<kLaunch>(p, z, idx, col);
+        if (run) {  // (a persistent launch is a plain one: the float4 surface, whole frames)
+            if (active) run->out[idx] = make_float4(col.x, col.y, col.z, 0.0f);
+        } else if (active) store_pixel<kLaunch>(p, z, idx, col);
     } else {
         const uint32_t pixel = static_cast<uint32_t>(y) * static_cast<uint32_t>(p.width) + static_cast<uint32_t>(x);
         v3 acc = mk(0.0f, 0.0f, 0.0f);
@@ -2203,9 +2226,10 @@ __device__ __forceinline__ void persistent_refill(const LaunchParams &p, float4 
 }
 // One item: wave tile (wx, wy) of view z, the view's records in the slot.
 template <int kShape, int kLaunch>
-__device__ __forceinline__ void persistent_tile(const LaunchParams &p, float4 *lds, int z, int wx, int wy) {
-    const float4 *blob = static_cast<const float4 *>(p.scene);
-    float4 *const slot = persistent_slot(p, lds);
+__device__ __forceinline__ void persistent_tile(const LaunchParams &p, float4 *lds, int z, int wx, int wy,
+                                                const RunTerms *run = nullptr) {
+    const float4 *blob = run ? run->blob : static_cast<const float4 *>(p.scene);
+    float4 *const slot = run ? run->slot : persistent_slot(p, lds);
     // (The Scene view is written out here and in render_kernel, field by field
     // in one order. Built by one inlined helper that the callers completed
     // with their view records, the same values reached the compiler in another
@@ -2255,9 +2279,9 @@ __device__ __forceinline__ void persistent_tile(const LaunchParams &p, float4 *l
     S.nb = L.n_boxes;
     S.nl = L.n_lights;
     S.nm = L.n_mats;
-    const FrameView V = cload((const __attribute__((address_space(4))) FrameView *)(p.views_dev) + z);
+    const FrameView V = cload(run ? run->view : (const __attribute__((address_space(4))) FrameView *)(p.views_dev) + z);
     const Ray none{mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f)};
-    render_wave_tile<0, false, kShape, kLaunch>(p, S, V, wx, wy, z, wave_pixel<kLaunch>(p, wx, wy), none, false);
+    render_wave_tile<0, false, kShape, kLaunch>(p, S, V, wx, wy, z, wave_pixel<kLaunch>(p, wx, wy, run), none, false, run);
 }
 // Timing probes (rt_internal.h kPadSalu, kPadValu; 0 by default): n more scalar
 // or vector adds per persistent tile, four independent chains on registers of
@@ -2301,9 +2325,66 @@ __device__ __forceinline__ void render_persistent0(float4 *lds) {
     const auto queue_waves = [](int q) {
         return persistent_queue_waves(q, static_cast<int>(gridDim.x) * (kThreads / 64));
     };
-    int held = -1;  // the view whose records the slot holds
+    [[maybe_unused]] int held = -1;  // the view whose records the slot holds (without tile runs)
     int c = persistent_first_chunk(global_wave());
-    for (;;) {
+    // Tile runs (rt_internal.h kTileRuns, TileRun): the chunk run by run. A
+    // run's head refills the slot where the view changes (and at the chunk's
+    // first run: at 1080p a wave's next chunk is four views on, so a check
+    // against the view held would hardly ever spare a refill there, and it
+    // kept a register live through every tile) and derives the RunTerms; a
+    // tile then reads the arguments only for the scene's layout, and the loop
+    // steps wx to the run's end: no frame edge to look for.
+    if constexpr (kTileRuns) for (;;) {
+        TileRun run;
+        int left;  // the chunk's items from the run's first on
+        {
+            const LaunchParams &p = launch_args();
+            const int wtx = (p.width + 7) / 8, wty = (p.height + 7) / 8;
+            const int total = wtx * wty * p.n_views;  // (< 2^30: persistent_groups)
+            const ChunkRange r_c = persistent_chunk(c, total, static_cast<int>(gridDim.x) * (kThreads / 64));
+            if (r_c.t >= r_c.t_end) break;
+            left = r_c.t_end - r_c.t;
+            run = persistent_first_run(r_c.t, left, wtx, wty);  // (the chunk's one division)
+            RT_PHASE_ONCE(1);  // the wave's first chunk
+            if (left == 1) RT_PHASE_ONCE(14);  // its first single tile
+            RT_PHASE_COUNT(15, 1);  // chunks
+            persistent_refill(p, lds, run.z);
+        }
+        for (;;) {
+            RunTerms T;
+            {
+                const LaunchParams &p = launch_args();
+                T.slot = persistent_slot(p, lds);
+                T.view = (const __attribute__((address_space(4))) FrameView *)(p.views_dev) + run.z;
+                T.blob = static_cast<const float4 *>(p.scene);
+                T.out = p.out + static_cast<size_t>(run.z) * p.height * p.width;
+                T.width = p.width;
+                T.height = p.height;
+                T.own_rows = (kShape & kShapeRoom) != 0;
+            }
+            for (int wx = run.wx, wx_end = run.wx + run.n; wx < wx_end; ++wx) {
+                const LaunchParams &p = launch_args();
+                RT_PHASE_COUNT(9, 1);  // tiles
+                persistent_pad(wx, run.wy, run.z, left);
+                persistent_tile<kShape, kLaunch>(p, lds, run.z, wx, run.wy, &T);
+            }
+            left -= run.n;
+            if (left <= 0) break;
+            const LaunchParams &p = launch_args();
+            const TileRun next = persistent_next_run(run, left, (p.width + 7) / 8, (p.height + 7) / 8);
+            if (next.z != run.z) persistent_refill(p, lds, next.z);
+            run = next;
+        }
+        {
+            // the queue's next chunk, taken only now that the wave needs it (below)
+            const LaunchParams &p = launch_args();
+            const int q = persistent_queue(global_wave());
+            int nxt = 0;
+            if ((threadIdx.x & 63) == 0) nxt = atomicAdd(p.sched + q * kQueueStride, 1);
+            c = (queue_waves(q) + __builtin_amdgcn_readfirstlane(nxt)) * kQueues + q;
+        }
+    }
+    if constexpr (!kTileRuns) for (;;) {
         int t, t_end, z, wx, wy;
         {
             const LaunchParams &p = launch_args();

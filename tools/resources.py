@@ -5,6 +5,12 @@
     python tools/resources.py --markdown [BUILD]          DESIGN.md §3's occupancy table
     python tools/resources.py --text BASE VARIANT         exit 1 unless both (.so or .o) hold the same device
                                                           functions with the same instructions
+    python tools/resources.py --census BUILD KERNEL [BEGIN [END]] [--blocks]
+                                                          the kernel's instruction mix (VALU, SALU, SMEM,
+                                                          branches, s_nop, v_readlane/v_writelane, ...): all
+                                                          of it, and from the first instruction matching the
+                                                          regular expression BEGIN to the next matching END;
+                                                          --blocks: every stretch between branches
 
 Reads the gfx950 code objects out of the library's .hip_fatbin section
 (llvm-objcopy + clang-offload-bundler) and its kernel metadata notes
@@ -148,6 +154,89 @@ def same_text(base, variant):
     return not odd
 
 
+CLASSES = ("valu", "salu", "smem", "branch", "s_nop", "lane", "lds", "vmem", "other")
+
+
+def classify(ins):
+    """The issue class of one disassembled instruction; "lane" (v_readlane / v_writelane, the spilled
+    SGPRs' traffic) is counted beside "valu", which holds it too."""
+    op = ins.split()[0]
+    if op.startswith(("s_load_", "s_buffer_load_")):
+        return "smem"
+    if op.startswith(("s_cbranch", "s_branch", "s_setpc", "s_swappc", "s_endpgm")):
+        return "branch"
+    if op == "s_nop":
+        return "s_nop"
+    if op.startswith(("s_waitcnt", "s_barrier", "s_setprio", "s_sleep", "s_sethalt", "s_trap", "s_code_end")):
+        return "other"
+    if op.startswith("s_"):
+        return "salu"
+    if op.startswith("ds_"):
+        return "lds"
+    if op.startswith(("global_", "buffer_", "flat_", "scratch_")):
+        return "vmem"
+    return "valu" if op.startswith("v_") else "other"
+
+
+def mix(instructions):
+    n = dict.fromkeys(CLASSES, 0)
+    for ins in instructions:
+        n[classify(ins)] += 1
+        if ins.startswith(("v_readlane", "v_writelane")):
+            n["lane"] += 1
+    return n
+
+
+def fmt_mix(n):
+    return "  ".join("%s %4d" % (k, n[k]) for k in CLASSES) + "  | all %d" % (sum(n.values()) - n["lane"])
+
+
+def kernel_text(spec, kernel):
+    """The instructions of the one kernel whose readable name (kernel_name) or mangled name is `kernel`."""
+    found = [(k, v) for k, v in texts(lib_path(spec)).items() if kernel in (k, kernel_name(k))]
+    if len(found) != 1:
+        sys.exit("%s: %d kernels named %s" % (spec, len(found), kernel))
+    return found[0][1]
+
+
+def blocks(instructions):
+    """The kernel's stretches between branches in layout order, [(first index, [instructions])]: a
+    new one begins behind every branch (the disassembly carries no labels, so a branch target inside
+    a stretch does not split it). Enough to find a loop's head and foot by their first instructions."""
+    out, cur, at = [], [], 0
+    for i, ins in enumerate(instructions):
+        if not cur:
+            at = i
+        cur.append(ins)
+        if classify(ins) == "branch":
+            out.append((at, cur))
+            cur = []
+    if cur:
+        out.append((at, cur))
+    return out
+
+
+def census(spec, kernel, begin=None, end=None, show_blocks=False):
+    """The instruction mix of a kernel: all of it, and from the first instruction that matches the
+    regular expression `begin` up to (not including) the next one behind it that matches `end` — a
+    loop's head to its first useful instruction, a vote site, ... in layout order. With show_blocks,
+    every stretch between branches with its first instruction, to find such anchors."""
+    ins = kernel_text(spec, kernel)
+    print("# %s %s" % (spec, kernel))
+    print("whole kernel     " + fmt_mix(mix(ins)))
+    if show_blocks:
+        for at, b in blocks(ins):
+            print("  @%-5d %-52s %s" % (at, b[0][:52], fmt_mix(mix(b))))
+    if begin:
+        lo = next((i for i, s in enumerate(ins) if re.search(begin, s)), None)
+        if lo is None:
+            sys.exit("no instruction matches %r" % begin)
+        hi = next((i for i in range(lo + 1, len(ins)) if end and re.search(end, ins[i])), len(ins))
+        print("[%d, %d)%s %s" % (lo, hi, " " * max(1, 14 - len("[%d, %d)" % (lo, hi))), fmt_mix(mix(ins[lo:hi]))))
+        return mix(ins[lo:hi])
+    return mix(ins)
+
+
 def fmt(name, r):
     return "%-28s VGPR %3d  SGPR %3d  scratch %4d B/lane  %d waves/SIMD" % (
         name, r.get("vgpr", -1), r.get("sgpr", -1), r.get("scratch", -1), r.get("waves_per_simd", 0))
@@ -224,6 +313,11 @@ def main():
         return
     if args[:1] == ["--text"]:
         sys.exit(0 if same_text(args[1], args[2]) else 1)
+    if args[:1] == ["--census"]:
+        show = "--blocks" in args
+        a = [x for x in args[1:] if x != "--blocks"]
+        census(a[0], a[1], a[2] if len(a) > 2 else None, a[3] if len(a) > 3 else None, show)
+        return
     if args[:1] == ["--gate"]:
         bad = gate(args[1], args[2])
         for k, x, y in bad:
