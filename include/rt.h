@@ -539,6 +539,43 @@ int rt_trace_rays(rt_context *ctx, const rt_scene *scene, const rt_ray *rays, in
  * stream with a host buffer: RT_ERR_INVALID). */
 int rt_view_rays(rt_context *ctx, const rt_view *view, int width, int height, int row_begin, int row_end,
                  rt_ray *rays, int rays_are_device, void *hip_stream);
+/* Occlusion (any-hit) queries: one bit per segment. Ray i is the segment
+ * origin + t * dir, 0 < t < 1: dir is the vector to the far end, used as given
+ * (the same rt_ray record as rt_trace_rays, so one buffer serves both calls).
+ * The segment is occluded iff get_closest_collision
+ * (raytrace_compute.glsl:738-782) of that ray returns an object with t < 1.0,
+ * the reference's shadow decision (:813-816); that is, iff rt_trace_rays would
+ * report hits[i].object >= 0 && hits[i].t < 1.0f, bit for bit, for every ray
+ * whose components are finite. It follows that
+ *  - a hit at t <= 0 is skipped (:753): a segment that starts exactly on a
+ *    surface is not blocked by that surface at t = 0;
+ *  - a hit at exactly t == 1.0f does not occlude;
+ *  - a segment that starts inside a sphere or box is blocked by the exit hit
+ *    when that lies below 1;
+ *  - the 10000 horizon plays no part;
+ *  - a ray with a non-finite component gets an unspecified answer for that
+ *    ray alone.
+ * Outputs, either may be NULL, not both: occluded[i], one byte per ray, 1 or
+ * 0; words[i / 64] bit i % 64 = ray i, (n_rays + 63) / 64 words, the bits past
+ * n_rays in the last word 0. Nothing beyond those counts is written.
+ * n_rays = 0 returns RT_OK and does nothing, once the arguments have passed
+ * the checks below (n_rays = 0 with both outputs NULL is RT_ERR_INVALID, as
+ * rt_trace_rays with no plane). buffers_are_device covers `rays`
+ * and both outputs; host buffers go through the context's grow-only ray
+ * buffer. hip_stream as in rt_trace_rays (a non-NULL stream: asynchronous,
+ * device buffers only). One launch on the call's stream, which stops at a
+ * segment's first blocker and searches no further than its far end.
+ * RT_OPT_CULLING applies and leaves the output identical (a wave of 64
+ * consecutive segments that holds an origin more than 1024 units from the
+ * world's origin on an axis, a |dir|^2 outside [2^-64, 2^64], or an origin
+ * farther from the scene's spheres than about 512 sqrt(r) units, r the
+ * smallest sphere's radius, tests every sphere: slower, identical); RT_OPT_OUTPUT does not apply; rt_last_kernel_ms
+ * covers the launch; the rt_debug_last_* hooks keep reporting the last render.
+ * Errors: RT_ERR_INVALID for a NULL context ("null context ..."), a NULL
+ * scene, a scene of another device, NULL rays with n_rays > 0, both outputs
+ * NULL, n_rays < 0 or > RT_MAX_RAYS, a stream with host buffers. */
+int rt_occluded(rt_context *ctx, const rt_scene *scene, const rt_ray *rays, int64_t n_rays, uint8_t *occluded,
+                uint64_t *words, int buffers_are_device, void *hip_stream);
 
 /* ---- one frame on several GPUs of this process ----
  * The reference renders a frame with one glDispatchCompute(W, H, 1) +

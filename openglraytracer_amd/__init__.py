@@ -100,6 +100,7 @@ def lib():
             "rt_aa_edge_mask": ([vp, i, i, f, vp, vp], i),
             "rt_trace_rays": ([vp, vp, vp, C.c_int64, i, i, vp, vp, vp, vp, i, vp], i),
             "rt_view_rays": ([vp, vp, i, i, i, i, vp, i, vp], i),
+            "rt_occluded": ([vp, vp, vp, C.c_int64, vp, vp, i, vp], i),
         }
         for name, (args, res) in sig.items():
             fn = getattr(L, name)
@@ -717,6 +718,43 @@ def trace_rays(ctx, scene, rays, max_depth=0, colors=True, hits=False, normals=F
     ptrs = [C.c_void_p(out[k].ctypes.data) if k in out else None for k in RAY_PLANES]
     _check(lib().rt_trace_rays(ctx.handle, scene.handle, C.c_void_p(a.ctypes.data), n, max_depth, flags, *ptrs, 0, sp))
     return tuple(out[k][:n] for k in RAY_PLANES if want[k])
+
+
+def occluded(ctx, scene, rays, packed=False, stream=None):
+    """rt_occluded: one bit per segment origin + t * dir, 0 < t < 1 (dir is the
+    vector to the far end): is any object in between? Equal to trace_rays'
+    (hits.object >= 0) & (hits.t < 1) for the same buffer.
+
+    rays: as trace_rays takes them. numpy in: a numpy bool array (n,) out,
+    synchronously. torch in: a torch uint8 tensor (n,) on the same device;
+    with `stream` (a hipStream_t as int) asynchronous on that stream.
+    packed=True: the bits as words instead, bit i % 64 of word i // 64,
+    (n + 63) // 64 of them: numpy uint64, or torch int64."""
+    sp = C.c_void_p(stream) if stream else None
+    if _is_torch(rays):
+        import torch
+        if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8:
+            raise ValueError("rays: a contiguous float32 tensor on the GPU, 8 values per ray")
+        if rays.device.index != ctx.device:
+            raise ValueError("rays: a tensor on the context's GPU (cuda:%d), not %s" % (ctx.device, rays.device))
+        n = rays.numel() // 8
+        m = (n + 63) // 64 if packed else n
+        out = torch.empty(max(m, 1), dtype=torch.int64 if packed else torch.uint8, device=rays.device)
+        ptrs = (None, C.c_void_p(out.data_ptr())) if packed else (C.c_void_p(out.data_ptr()), None)
+        _check(lib().rt_occluded(ctx.handle, scene.handle, C.c_void_p(rays.data_ptr()), n, *ptrs, 1, sp))
+        return out[:m]
+    a = np.ascontiguousarray(rays)
+    if a.dtype != abi.RAY_DTYPE:
+        a = np.ascontiguousarray(a, np.float32)
+        if a.size % 8:
+            raise ValueError("rays: abi.RAY_DTYPE records, or 8 float32 values per ray")
+        a = a.reshape(-1, 8)
+    n = a.size if a.dtype == abi.RAY_DTYPE else a.shape[0]
+    m = (n + 63) // 64 if packed else n
+    out = np.zeros(max(m, 1), np.uint64 if packed else np.uint8)
+    ptrs = (None, C.c_void_p(out.ctypes.data)) if packed else (C.c_void_p(out.ctypes.data), None)
+    _check(lib().rt_occluded(ctx.handle, scene.handle, C.c_void_p(a.ctypes.data), n, *ptrs, 0, sp))
+    return out[:m] if packed else out[:m].astype(bool)
 
 
 def view_rays(ctx, view, width, height, rows=None, device=False):

@@ -865,6 +865,23 @@ constexpr float kRayUnitDir = 0x1p-19f;
 hipError_t launch_rays(LaunchParams &p, const RayTargets &o, int max_depth, hipStream_t stream);
 // ray_hits_kernel over o.n_rays rays (hits, normals, points).
 hipError_t launch_ray_hits(LaunchParams &p, const RayTargets &o, hipStream_t stream);
+// Occlusion queries (rt_occluded): the second kernel argument of
+// occluded_kernel. `rays` as RayTargets has them, read as segments origin +
+// t * dir, 0 < t < 1. `bytes`: one byte per ray (1 occluded, 0 not); `words`:
+// bit i % 64 of word i / 64, (n_rays + 63) / 64 words; either may be nullptr.
+struct OccludedTargets {
+    const float4 *rays;
+    uint8_t *bytes;
+    uint64_t *words;
+    int64_t n_rays;  // 1..RT_MAX_RAYS
+    int32_t cull;    // RT_OPT_CULLING
+    int32_t pad;
+};
+static_assert(sizeof(OccludedTargets) == 40 && sizeof(LaunchParams) + sizeof(OccludedTargets) <= 6144,
+              "kernel argument block");
+// occluded_kernel over o.n_rays segments, 256 per work-group (rt_kernel.hip
+// segment_walk_slack derives when a segment walks the sphere BVH).
+hipError_t launch_occluded(LaunchParams &p, const OccludedTargets &o, hipStream_t stream);
 // view_rays_kernel: the camera rays of p.view[0] for rows [p.row_begin,
 // p.row_begin + p.n_rows) of a p.width x p.height frame, in pixel order.
 hipError_t launch_view_rays(const LaunchParams &p, float4 *rays, hipStream_t stream);

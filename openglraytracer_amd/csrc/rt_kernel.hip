@@ -2986,6 +2986,176 @@ void ray_hits_kernel(LaunchParams p, RayTargets o) {
     if (o.points) o.points[at] = hit ? make_float4(c.p.x, c.p.y, c.p.z, 0.0f) : zero;
 }
 
+// ---- occlusion queries (rt_occluded) -----------------------------------------
+// Is there an object with 0 < t < 1 along start + t * dir, for a segment with
+// no light attached: occluded_impl's question without the per-light culling
+// data (cones, direction masks, box planes), which an arbitrary segment cannot
+// use. The exact tests are occluded_impl's own (box_occludes with no light bit
+// and no room, sphere_blocks), so a lane's answer is "some object's exact test
+// says 0 < t < 1", which is the closest hit's object >= 0 && t < 1: closer()
+// takes the least t > 0 below 10000 of the same t values.
+//
+// Spheres with culling on: an any-hit walk of the LDS sphere BVH in
+// closest_impl's order (octant links, while-while), the node test bounded by
+// the segment's end, t_limit = 1, a lane leaving at its first blocker.
+//
+// When that walk is conservative (segment_walk_slack). Two things must hold
+// for every sphere whose exact test answers 0 < t' < 1: the node test's own
+// error stays under the boxes' margin, and the point the exact test found lies
+// in a box the node test looks at.
+// (1) The node test. node_hit's derivation is written for unit directions but
+// uses the length in one place only, that v_rcp does not flush. Everything
+// else is in units of position: a plane's computed distance times |d_axis| is
+// off by e_node = 1.8e-7 (|o| + |x|) + 6e-8 |o|, whatever |d| is, because
+// t |d_axis| = |x - o| for a plane x of a node, and the nodes lie in the scene,
+// not along the segment. (Scaling dir by 2^k scales id, oid and every t by
+// 2^-k exactly.) So e_node < 2.5e-4 + 2e-7 |x| under the margin m = 1e-3 +
+// 1e-4 |x| for |o| <= kRayNearOrigin per axis, as for the ray kernels, and the
+// far end o + dir needs no bound beyond the one on |dir|. If the true point
+// P(t*) = o + t* dir lies inside a sphere's own box at a real 0 <= t* <= 1,
+// every ancestor's slabs hold it with m to spare, so per axis near' <= t* <=
+// far': tn' <= tf', tf' >= 0 and tn' <= 1. The limit needs no slack.
+// (2) The exact test's root, tangency included. With u = 2^-24, R = |o - c|,
+// D = |dir| and the true quadratic g(t) = |P(t) - c|^2 - r^2 = qa t^2 + B t +
+// C: for any t, g(t) = (s^2 - Delta) / (4 qa) with s = 2 qa t + B and Delta
+// the true discriminant. The computed root is t' = (-qb' +- sq')(1 + e) /
+// (2 qa'), |e| <= 3u, qa' = qa (1 + 3u), so s' = +-sq'(1 + 6u) + eta with
+// |eta| <= |B - qb'| + 6u |qb'| <= 22u D R (oc's rounding and the dot
+// product's: 10u D R). sq'^2 = qd'(1 + 2u), qd' = Delta + delta, |delta| <=
+// 88u D^2 R^2 (qb'^2: 44u; qa4' qc': 40u with qc' = C + 6u R^2; the
+// subtraction: 4u), |sq'| <= 2 D R. Together |s'^2 - Delta| <= (88 + 60 + 88
+// + ...) u D^2 R^2 < 2^-16 D^2 R^2, so | |P(t') - c|^2 - r^2 | < 2^-18 R^2
+// whatever the sign of the true discriminant: P(t') lies within 2^-19 R^2 / r
+// of the sphere (sqrt(r^2 + E) <= r + E / 2r), so inside its box grown by
+// that much. At R = 300, r = 1 that is 0.17, far above m: a segment that ends
+// just before a far sphere's tangent foot is "blocked" by rounding while the
+// plain node test has tn > 1. Hence the slack: the walk tests every node box
+// grown, per lane, by slack = 2^-18 Rm^2 / r_min (twice the bound: the
+// slack's own float arithmetic and the grown planes' rounding, 6e-8 |x|, are
+// far inside the factor), with r_min the least sqrt(c.w) of the scene's
+// spheres (the radius the leaf boxes were built around, build_bvh) and Rm =
+// |o - centre| + half the diagonal of the root node's box >= |o - c| for
+// every sphere in the tree. Then t* = t' serves (1). A few 1e-3 in a scene
+// of +-10 units; a lane whose slack exceeds kOccSlackMax (a far origin, a
+// tiny sphere; r_min = 0 or NaN) sends its wave to the exhaustive loop, for
+// there the grown boxes cull little.
+// (3) The float range: |dir|^2 in [2^-64, 2^64] keeps rcp(d_a) of every
+// component above 1e-30 normal, every x * id below 2^11 * 2^100, the margin in
+// t (>= 1e-3 * 2^-32) and the sphere test's qa4 far from the ends of the
+// range (root_floor's fast path and its fallback have the same form t' =
+// fl(n' / qa2'), which (2) covers).
+// A wave that holds a segment outside any of these (or a non-finite one: NaN
+// and inf fail the comparisons) runs the exhaustive loop instead, where each
+// sphere takes the exact test; any-hit over the same exact tests, so the
+// same answers. Termination: the box and sphere loops are counted, and the
+// walk follows forward-only links (node_hit), whatever the tests answer.
+constexpr float kOccDirMin = 0x1p-64f, kOccDirMax = 0x1p64f;  // |dir|^2
+constexpr float kOccSlackMax = 1.0f;
+// The least c.w of the scene's spheres (a NaN is passed over: such a sphere's
+// exact test never answers). Called with all lanes active.
+__device__ __forceinline__ float least_radius2(const Scene &S) {
+    float rr = __builtin_inff();
+    for (int k = threadIdx.x & 63; k < S.ns; k += 64) rr = fminf(rr, S.sph[k].w);
+    return wave_min(rr);
+}
+// The lane's slack, or a NaN / a value above kOccSlackMax: no walk for its wave.
+__device__ __forceinline__ float segment_walk_slack(const Scene &S, const Ray &r, float rr_min) {
+    const float qa = dot(r.dir, r.dir);
+    const bool in = fabsf(r.start.x) <= kRayNearOrigin && fabsf(r.start.y) <= kRayNearOrigin &&
+                    fabsf(r.start.z) <= kRayNearOrigin && qa >= kOccDirMin && qa <= kOccDirMax;  // (NaN fails)
+    const float4 lo = S.bvh[0], hi = S.bvh[1];  // the root node: every sphere of the tree
+    const v3 half = muls(sub(mk(hi.x, hi.y, hi.z), mk(lo.x, lo.y, lo.z)), 0.5f);
+    const v3 off = sub(r.start, add(mk(lo.x, lo.y, lo.z), half));
+    const float rm = sqrtf(dot(off, off)) + sqrtf(dot(half, half));
+    const float slack = fdiv(0x1p-18f * rm * rm, sqrtf(rr_min));
+    return in ? slack : __builtin_nanf("");
+}
+// Called with all lanes active; `cull`: wave-uniform; `slack`: the lane's, read when `cull`.
+__device__ __forceinline__ bool segment_occluded(const Scene &S, const Ray &r, bool need, bool cull, float slack) {
+    bool hit = false;
+    for (int b = 0; b < S.nb; ++b) {
+        if (!wave_any(need && !hit)) return hit;
+        // (every lane tests: box_occludes votes on its pre-test, and skips the
+        // exact slab test in a wave none of whose lanes can hit the box)
+        const bool occ = box_occludes(cload(S.cbox + b), r.start, r.dir, 0u, false, cull);
+        hit = hit | (need & occ);
+    }
+    if (!wave_any(need && !hit)) return hit;
+    const v3 d2 = muls(r.dir, 2.0f);
+    const float qa = dot(r.dir, r.dir);
+    const float qa2 = 2.0f * qa, qa4 = 4.0f * qa;
+    const float floor = root_floor(qa2);
+    const auto blocks = [&](int s) {
+        const float4 c = S.sph[s];
+        const v3 oc = sub(r.start, mk(c.x, c.y, c.z));
+        return sphere_blocks(dot(d2, oc), dot(oc, oc) - c.w, qa2, qa4, floor);
+    };
+    if (cull && S.nbvh > 0) {
+        const RayInv q = ray_inv(r);
+        int node = need && !hit ? 0 : -1;
+        int held = 0;  // (count << 24) | first sphere of the held leaf
+        const int oct = (r.dir.x < 0.0f ? 1 : 0) | (r.dir.y < 0.0f ? 2 : 0) | (r.dir.z < 0.0f ? 4 : 0);
+        // while-while, as closest_impl: a lane walks until it holds a leaf,
+        // then the wave tests the held leaves together
+        while (wave_any(node >= 0)) {
+            while (node >= 0 && held == 0) {
+                float4 lo = S.bvh[2 * node], hi = S.bvh[2 * node + 1];
+                const uint32_t link = S.blink[node * kBvhOctants + oct];
+                const int leaf = __float_as_int(hi.w);
+                lo = make_float4(lo.x - slack, lo.y - slack, lo.z - slack, 0.0f);
+                hi = make_float4(hi.x + slack, hi.y + slack, hi.z + slack, 0.0f);
+                if (node_hit(q, lo, hi, 1.0f)) {
+                    held = leaf;
+                    node = static_cast<int16_t>(link & 0xFFFFu);
+                } else {
+                    node = static_cast<int16_t>(link >> 16);
+                }
+            }
+            if (held) {
+                const int first = held & 0xFFFFFF, count = held >> 24;
+                for (int s = first; s < first + count; ++s)
+                    if (!hit) hit = blocks(s);
+                held = 0;
+                if (hit) node = -1;  // the first blocker ends the lane's walk
+            }
+        }
+        return hit;
+    }
+    for (int s = 0; s < S.ns; ++s) {
+        if (!wave_any(need && !hit)) break;
+        if (need && !hit) hit = blocks(s);
+    }
+    return hit;
+}
+
+// One bit per segment: the ray kernels' prologue, the decision above, and a
+// byte per active lane and / or the wave's ballot as one 64-bit word (lane 0
+// of a wave with an active lane is active: the rays are in lane order), whose
+// bits past the last ray come from inactive lanes and are 0.
+__global__ __launch_bounds__(kThreads) void occluded_kernel(LaunchParams p, OccludedTargets o) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds[];
+    size_t at;
+    bool active;
+    RayTargets in{};
+    in.rays = o.rays;
+    in.n_rays = o.n_rays;
+    const Ray ray = ray_prologue(p, in, lds, at, active);
+    if (!wave_any(active)) return;  // (a wave past the last ray; the barrier is behind it)
+    const Scene S = ray_scene<false>(p, lds, static_cast<const float4 *>(p.scene), o.cull);
+    bool cull = o.cull != 0;
+    float slack = 0.0f;
+    if (cull && S.nbvh > 0) {
+        slack = segment_walk_slack(S, ray, least_radius2(S));
+        cull = !wave_any(active && !(slack <= kOccSlackMax));  // (NaN fails)
+    }
+    const bool hit = segment_occluded(S, ray, active, cull, slack) && active;
+    if (o.bytes && active) o.bytes[at] = hit ? 1 : 0;
+    if (o.words) {
+        const uint64_t bits = wave_ballot(hit);
+        if ((threadIdx.x & 63) == 0) o.words[at >> 6] = bits;
+    }
+}
+
 // rt_view_rays: the camera rays of view 0, camera_ray's text with no jitter,
 // one thread per pixel of the launch's rows in rt_render's pixel order.
 __global__ __launch_bounds__(kThreads) void view_rays_kernel(LaunchParams p, float4 *rays) {
@@ -3426,6 +3596,18 @@ hipError_t launch_ray_hits(LaunchParams &p, const RayTargets &o, hipStream_t str
     return launch_ray_fn(reinterpret_cast<const void *>(&ray_hits_kernel), p, o, stream);
 }
 
+hipError_t launch_occluded(LaunchParams &p, const OccludedTargets &o, hipStream_t stream) {
+    if (o.n_rays <= 0 || o.n_rays > RT_MAX_RAYS || !o.rays || (!o.bytes && !o.words)) return hipErrorInvalidValue;
+    p.sched = nullptr;
+    OccludedTargets targets = o;
+    void *args[] = {&p, &targets};
+    const dim3 grid(static_cast<unsigned>((o.n_rays + kThreads - 1) / kThreads), 1, 1);  // <= 2^20
+    const hipError_t e = hipLaunchKernel(reinterpret_cast<const void *>(&occluded_kernel), grid, dim3(kThreads), args,
+                                         static_cast<size_t>(p.layout.blob_units) * sizeof(float4), stream);
+    (void)hipGetLastError();  // (e is the launch's own status; no sticky error for a later check)
+    return e;
+}
+
 hipError_t launch_view_rays(const LaunchParams &p, float4 *rays, hipStream_t stream) {
     LaunchParams q = p;
     void *args[] = {&q, &rays};
@@ -3650,6 +3832,8 @@ hipError_t allow_large_lds(size_t bytes) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   static_cast<int>(bytes));
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ray_hits_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&occluded_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
     for (const AaRefineFn fn : kAaRefine)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
